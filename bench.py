@@ -4,22 +4,26 @@
 A step = one send proof per rank through libzkgpu.so's prover — the equivalent of one `r1cs_gg_ppzksnark_prover(pk, primary, auxiliary)` call (reference
 r1cs_gg_ppzksnark.tcc:391-506) — on the next of the run's distinct statements, all of them RESIDENT IN HBM as raw assignments when the timed region starts
 (`zkgpu_prover_prove_stashed`: everything the prover derives from an assignment, the classification of multiexp.tcc:443-496 included, happens inside the timed call), and the
-serialized proof comes back.  The same call handed a fresh HOST buffer every step is timed right after it with the same steps, barriers and percentiles
+serialized proof comes back.  With --full, the same call handed a fresh HOST buffer every step is timed right after it with the same steps, barriers and percentiles
 (`value_from_host_buffers`).  N ranks prove independent seeded instances (proofs are independent units: no data-path collective), so value = N*K proofs / max-over-ranks wall
 time ("weak" scaling).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
         N > 1 without a launcher: this script starts the N ranks itself (child processes, one per GPU, created before
         anything in the parent touches the GPU) and exits with their status.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
         (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment; --gpus must equal WORLD_SIZE)
 
 Prints ONE JSON line on rank 0's stdout (everything else, including the reference-style chatter of the cgo symbols,
-goes to stderr).  `roofline` times the dominant kernel (bucket accumulation of the H-query MSM) with HIP events on the
-library's compute stream; `cpu_baseline` times the reference's own prover (oracle/_ref, kind "reference") on the host
-cores, or the plain-C oracle (kind "port") where that binary is absent.
+goes to stderr).  A plain run ends with that line after the timed steps; --dump-outputs DIR first writes the proof of
+the last timed step to DIR/proof.npy (float64 (8, 32): the 512-character proof's eight 256-bit coordinates, one byte per
+value).  Statement k (step i proves statement i mod the number of distinct statements, on every path) is proved with the
+fixed full-width (r, s) of workload.prover_rs(k), two seeded values below the group order: equal arguments give equal proofs.
+--full adds the rest, after the timed steps: the check of the last proof, the host-buffer leg, the extra legs, `roofline`
+(the dominant kernel, bucket accumulation of the H-query MSM, timed with HIP events on the library's compute stream) and
+`cpu_baseline` (the reference's own prover, oracle/_ref, kind "reference", or the plain-C oracle, kind "port").
 """
-import argparse, json, os, socket, subprocess, sys, tempfile, time
+import argparse, json, os, shutil, socket, subprocess, sys, tempfile, time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -28,18 +32,23 @@ H_PAIRS = 262143                       # H-query size of the send circuit (m - 1
 BYTES_PER_G1_PAIR = 96                 # 64 B affine point + 32 B scalar, each read once
 HBM_PEAK_GBS = 8000.0                  # MI355X_MICROARCH.md: 8 TB/s
 MAX_DISTINCT_WITNESSES = 64            # host memory bound (7.3 MB each); longer runs cycle through them, consecutive steps still differ
+SCRATCH = []                           # temporary directories of this process: removed when it ends, however it ends (main)
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
 
 def parse_args():
     ap = argparse.ArgumentParser(); ap.add_argument("--gpus", type=int, default=1); ap.add_argument("--steps", type=int, default=50); ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the proof of the last timed step to DIR/proof.npy (float64, one value per byte)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also check the last proof and run the host-buffer, extra, roofline and CPU-baseline legs")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra-legs", action="store_true", help="only the timed region and the roofline leg (what the N > 1 scaling runs need)")
     ap.add_argument("--inflight", type=int, default=6, help="extra leg (not `value`): this many prover objects per GPU, one host thread each, proofs overlapping on the device; 0/1 = skip")
     ap.add_argument("--batch", type=int, default=64, help="extra leg (not `value`): zkgpu_prover_prove_batch with this many witnesses per call (BASELINE.json configs[2]); 0/1 = skip")
     ap.add_argument("--shard-msm", action="store_true", help="N > 1 only: all ranks prove ONE proof per step together, each holding 1/N of every query; one all-gather of 384-byte partial records per proof (strong scaling)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0: ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 def launch(args):
     """--gpus N without a launcher: start the N ranks as child processes.  Nothing here imports torch or touches HIP, so no process that initialised the GPU is ever
@@ -65,6 +74,12 @@ def read_witness(path):
     """[u64 n | n * 32 bytes] as written by libzkgpu's witness generators -> (n, 4) uint64 canonical values"""
     import numpy as np
     b = open(path, "rb").read(); n = int(np.frombuffer(b, dtype=np.uint64, count=1)[0]); return np.frombuffer(b, dtype=np.uint64, count=4 * n, offset=8).reshape(n, 4).copy()
+
+def dump_proof(out_dir, name, proof_hex):
+    """512 hex characters -> out_dir/<name>.npy: float64 (8, 32), one 256-bit coordinate a row, one big-endian byte a value (exact in float64)"""
+    import numpy as np
+    assert len(proof_hex) == 512, "not a serialized proof: %r" % proof_hex[:80]
+    os.makedirs(out_dir, exist_ok=True); np.save(os.path.join(out_dir, name + ".npy"), np.frombuffer(bytes.fromhex(proof_hex), dtype=np.uint8).reshape(8, 32).astype(np.float64))
 
 def usable_cores():
     """host cores this process may really use: the affinity mask, capped by the cgroup CPU quota (a pod that sees 256 CPUs may own far fewer; oversubscribed OpenMP
@@ -164,9 +179,9 @@ def run_rank(args):
             if grp is not None: log("bench: rank %d leaves: a rank failed at '%s'" % (rank, name)); grp.close()
             raise SystemExit(3)
         return out
-    tmp = tempfile.mkdtemp(prefix="zkbench_%d_" % rank); shard = args.shard_msm and world > 1; t_keygen = 0.0
+    tmp = tempfile.mkdtemp(prefix="zkbench_%d_" % rank); SCRATCH.append(tmp); shard = args.shard_msm and world > 1; t_keygen = 0.0
     def make_key():
-        kd = tmp if world == 1 else tempfile.mkdtemp(prefix="zkbench_key_"); t0 = time.time(); e.keygen("send", os.path.join(kd, "sendpk.txt"), os.path.join(kd, "sendvk.txt"), seed=0xB10C4A2E); return kd, time.time() - t0
+        kd = tmp if world == 1 else tempfile.mkdtemp(prefix="zkbench_key_"); SCRATCH.append(kd); t0 = time.time(); e.keygen("send", os.path.join(kd, "sendpk.txt"), os.path.join(kd, "sendvk.txt"), seed=0xB10C4A2E); return kd, time.time() - t0
     made = stage("keygen", make_key if rank == 0 else (lambda: None))
     if rank == 0: key_dir, t_keygen = made
     if grp is not None: key_dir = grp.share_from_rank0(key_dir if rank == 0 else None)
@@ -190,10 +205,11 @@ def run_rank(args):
         if torch.cuda.is_available(): torch.cuda.synchronize()
 
     remade = []                                                               # statements whose stash had to be made a second time (stash_failed below): none, normally
+    rs_int = [w.prover_rs(k) for k in range(n_inst)]; rs = [(r.to_bytes(32, "little"), s_.to_bytes(32, "little")) for r, s_ in rs_int]     # the fixed full-width (r, s) of statement k
     if shard:
         def one_proof(i):                                                      # every rank runs the device pipeline on its slice; 384 B per rank are exchanged; rank 0 assembles
             prover.set_witness(zs[i % n_inst]); recs = grp.gather_partials(prover.prove_partial())
-            return prover.finish(recs, 0x1234567 + i, 0x7654321 + i) if rank == 0 else None
+            return prover.finish(recs, *rs_int[i % n_inst]) if rank == 0 else None
     else:
         # host buffer in, fresh (r, s), serialized proof (512 hex characters) out; synchronous.  The C entry point is called with argument objects built once: what is timed
         # is the library, not numpy's contiguity checks and a Python string per step (20-25 us of a 1.1 ms step); the buffer of the last call is decoded for the verification below
@@ -219,12 +235,12 @@ def run_rank(args):
             if len(remade) >= 3: raise RuntimeError("zkgpu_prover_prove_stashed failed again after %d stashes were made anew: %s" % (len(remade), msg))
             if _lib.zkgpu_prover_prove(_h, _zp[k], None, None, _out) != 0: raise RuntimeError("statement %d is not provable from its host buffer either: %s" % (k, _lib.zkgpu_last_error().decode()))
             prover.set_witness(zs[k]); slots[k] = ctypes.c_uint32(prover.stash_witness()); remade.append(k)
-            if _lib.zkgpu_prover_prove_stashed(_h, slots[k], None, None, _out) != 0: raise RuntimeError("zkgpu_prover_prove_stashed failed on a stash made anew: %s" % _lib.zkgpu_last_error().decode())
+            if _lib.zkgpu_prover_prove_stashed(_h, slots[k], rs[k][0], rs[k][1], _out) != 0: raise RuntimeError("zkgpu_prover_prove_stashed failed on a stash made anew: %s" % _lib.zkgpu_last_error().decode())
             return _out
         if fail_at.startswith("stash:"):                                      # tests only: statement <k>'s stash holds one wrong value — the step that meets it must say so, make it anew and go on
             k = int(fail_at.split(":")[1]) % n_inst; wrong = zs[k].copy(); wrong[5000 % len(wrong)] = (3, 0, 0, 0); prover.set_witness(wrong); prover.drop_stash(slots[k].value); slots[k] = ctypes.c_uint32(prover.stash_witness())
         def one_proof(i):
-            rc = _lib.zkgpu_prover_prove_stashed(_h, slots[i % n_inst], None, None, _out)
+            k = i % n_inst; rc = _lib.zkgpu_prover_prove_stashed(_h, slots[k], rs[k][0], rs[k][1], _out)
             return _out if rc == 0 else stash_failed(i)
     # (the interpreter's cycle collector stays out of the timed region: with torch and numpy loaded a full pass is ~10 ms — thirteen proofs — and its timing is a matter of
     # allocation counts; nothing in the loop makes cycles.  Collected once here, switched back on after the clock stops.)
@@ -239,10 +255,12 @@ def run_rank(args):
     last = None; step_t[0] = t0
     for i in range(args.steps): last = one_proof(args.warmup + i); step_t[i + 1] = clock()        # (one clock read per step: the spread of the timed region goes into the line)
     barrier(); dt = clock() - t0; gc.enable()
+    if last is not None and not isinstance(last, str): last = last.value.decode()               # (here: the host-buffer leg writes into the same buffer)
+    if args.dump_outputs and last is not None: dump_proof(args.dump_outputs, "proof" if rank == 0 else "proof_rank%d" % rank, last)
     # the same prover call handed a fresh HOST buffer every step (scan of the 7.3 MB assignment into its compact form, one 0.3 MB copy over PCIe, the expansion on the
     # device): the same K steps, the same barriers, the same percentiles, in every mode — `value_from_host_buffers`, what rounds 1-4 reported as `value`
     hb_rate = hb_step_ms = None
-    if not shard:
+    if args.full and not shard:
         gc.collect(); gc.disable()
         for i in range(args.warmup): host_buffer_proof(i)
         hb_t = [0.0] * (args.steps + 1); barrier(); hb_t[0] = clock()
@@ -256,7 +274,23 @@ def run_rank(args):
     per_step = sorted(1e3 * (b - a) for a, b in zip(step_t, step_t[1:])); pct = lambda q: round(per_step[min(len(per_step) - 1, int(q * len(per_step)))], 4) if per_step else None
     step_ms = {"p10": pct(0.10), "p50": pct(0.50), "p90": pct(0.90), "min": round(per_step[0], 4) if per_step else None, "max": round(per_step[-1], 4) if per_step else None, "rank": rank}
     d = insts[(args.warmup + args.steps - 1) % n_inst]
-    if last is not None and not isinstance(last, str): last = last.value.decode()
+    def finish():                                                             # the line on rank 0, then the end of the run
+        if rank == 0:
+            line = {
+                "metric": "Groth16 proofs/sec (send circuit, alt_bn128)", "value": round(rate, 4), "unit": "proofs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+                "ms_per_step": round(1e3 * dt / args.steps, 4), "step_ms": step_ms, "value_p50": (round(1e3 / step_ms["p50"] * (1 if shard else world), 4) if step_ms.get("p50") else None), "higher_is_better": True, "full": args.full, "scaling": "strong" if shard else "weak", "vs_baseline": None, "dtype": "u32 limbs (254-bit Fq/Fr Montgomery; all MSM accumulations, the H query's weighted bucket sum and the transforms' tiles on nine 29-bit limbs)", "data": "synthetic witnesses (seeded send instances, every constraint satisfied) on a proving key made by this repo's GPU generator for the real send circuit; only the libsnark CPU leg uses a key with synthetic points of the same shape",
+                "config": {"workload": "send circuit single proof per step (252,286 constraints, domain 2^18; BASELINE.json configs[1])", "proofs_per_step": 1 if shard else world, "distinct_witnesses": n_inst,
+                           "host_binding": host_binding, "stash_remade": len(remade), "clock_warmup": "%d untimed proofs ahead of the %d warm-up steps (the GPU's clocks need ~30 ms of load to rise after the idle set-up)" % (clock_warmup, args.warmup), "parallelism": ("one proof per step, every query cut into %d contiguous shards, one all-gather of 384 B per rank" % world) if shard else "independent proofs per GPU, no collective",
+                           "includes": "one prover call per step on the next of the run's distinct statements, all of them RESIDENT IN HBM when the timed region starts (handed over before the clock starts, kept in device memory as the raw vector; a step classifies its assignment on the device and proves it in place): the classification of the values (0 / 1 / other), R1CS rows, the 7 NTTs of the witness map (4 run per proof; both transforms of C and the final inverse are folded into the L and H queries at key load), 5 MSM, host proof assembly, hex serialisation; excludes witness generation and key load.  `value_p50` = 1 / the median step (the mean carries the host's rare 2-5 ms steps); `value_from_host_buffers` (with --full) = the same prover call handed a fresh host buffer every step (scan + PCIe + expansion included; N = 1 only) — what rounds 1-4 reported as `value`" if not shard else "one proof per step cut into shards; host-buffer hand-over included"},
+                "ranks": rank_info, "prover_timings_ms": prover.timings(), "setup_s": {"keygen": round(t_keygen, 2), "key_load": round(t_load, 2), "hbm": hbm or None}}
+            if args.full:
+                line.update({"value_from_host_buffers": (round(hb_rate, 4) if hb_rate else None), "host_buffers_step_ms": hb_step_ms, "roofline": roofline, "roofline_valu": roofline_valu, "cpu_baseline": cpu,
+                             "cpu_baseline_variants": cpu_more or None, "extra_legs": extra or None, "stage_ms_per_proof": {k: round(v, 4) for k, v in sorted(per_proof.items())}})
+            real_stdout.write(json.dumps(line) + "\n"); real_stdout.flush()
+        prover.close()
+        if grp is not None: barrier(); grp.close()                           # (every rank is done with rank 0's key before main removes it)
+        return 0
+    if not args.full: return finish()                                         # a plain run: nothing after the timed steps
     assert last is None or e.verify(vk_path, last, w.pack_public([d["cmtA_old"], d["sn_old"], d["cmtS"], d["cmtA"]])), "proof from the timed region does not verify"
 
     extra = {}; cpu_files = {}                                     # cpu_files: circuit legs whose libsnark time is reported beside them
@@ -413,25 +447,15 @@ def run_rank(args):
             cs = o.R1CS.load(r1cs_path); cs = cs.swapped() if cs.swap_ab_beneficial() else cs; pk, _ = o.parse_pk(pk_path); t0 = time.time(); o.prove(cs, zs[0], pk, 12345, 67890); t = time.time() - t0
             cpu = {"value": round(1.0 / t, 5), "unit": "proofs/s", "cores": 1, "kind": "port", "sample": "1 send proof by the plain-C oracle prover; %.2f s" % t}
 
-    if rank == 0:
-        line = {
-            "metric": "Groth16 proofs/sec (send circuit, alt_bn128)", "value": round(rate, 4), "unit": "proofs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(1e3 * dt / args.steps, 4), "step_ms": step_ms, "value_p50": (round(1e3 / step_ms["p50"] * (1 if shard else world), 4) if step_ms.get("p50") else None), "value_from_host_buffers": (round(hb_rate, 4) if hb_rate else None), "host_buffers_step_ms": hb_step_ms, "higher_is_better": True, "scaling": "strong" if shard else "weak", "vs_baseline": None, "dtype": "u32 limbs (254-bit Fq/Fr Montgomery; all MSM accumulations, the H query's weighted bucket sum and the transforms' tiles on nine 29-bit limbs)", "data": "synthetic witnesses (seeded send instances, every constraint satisfied) on a proving key made by this repo's GPU generator for the real send circuit; only the libsnark CPU leg uses a key with synthetic points of the same shape",
-            "config": {"workload": "send circuit single proof per step (252,286 constraints, domain 2^18; BASELINE.json configs[1])", "proofs_per_step": 1 if shard else world, "distinct_witnesses": n_inst,
-                       "host_binding": host_binding, "stash_remade": len(remade), "clock_warmup": "%d untimed proofs ahead of the %d warm-up steps (the GPU's clocks need ~30 ms of load to rise after the idle set-up)" % (clock_warmup, args.warmup), "parallelism": ("one proof per step, every query cut into %d contiguous shards, one all-gather of 384 B per rank" % world) if shard else "independent proofs per GPU, no collective",
-                       "includes": "one prover call per step on the next of the run's distinct statements, all of them RESIDENT IN HBM when the timed region starts (handed over before the clock starts, kept in device memory as the raw vector; a step classifies its assignment on the device and proves it in place): the classification of the values (0 / 1 / other), R1CS rows, the 7 NTTs of the witness map (4 run per proof; both transforms of C and the final inverse are folded into the L and H queries at key load), 5 MSM, host proof assembly, hex serialisation; excludes witness generation and key load.  `value_p50` = 1 / the median step (the mean carries the host's rare 2-5 ms steps); `value_from_host_buffers` = the same prover call handed a fresh host buffer every step (scan + PCIe + expansion included; N = 1 only) — what rounds 1-4 reported as `value`" if not shard else "one proof per step cut into shards; host-buffer hand-over included"},
-            "ranks": rank_info, "roofline": roofline, "roofline_valu": roofline_valu, "cpu_baseline": cpu, "cpu_baseline_variants": cpu_more or None, "extra_legs": extra or None,
-            "stage_ms_per_proof": {k: round(v, 4) for k, v in sorted(per_proof.items())}, "prover_timings_ms": prover.timings(), "setup_s": {"keygen": round(t_keygen, 2), "key_load": round(t_load, 2), "hbm": hbm or None}}
-        real_stdout.write(json.dumps(line) + "\n"); real_stdout.flush()
-    prover.close()
-    if grp is not None: grp.close()
-    return 0
+    return finish()
 
 def main():
     args = parse_args()
     if args.gpus < 1: log("bench: --gpus must be >= 1"); return 2
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ: return launch(args)
-    return run_rank(args)
+    try: return run_rank(args)
+    finally:
+        for d in SCRATCH: shutil.rmtree(d, ignore_errors=True)               # the run's keys, key containers and witness files
 
 if __name__ == "__main__":
     sys.exit(main())

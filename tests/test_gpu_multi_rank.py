@@ -7,7 +7,7 @@ pytestmark = pytest.mark.gpu
 
 def run(args, timeout=900):
     e = dict(os.environ, ZK_BENCH_BACKEND="gloo"); e.pop("RANK", None); e.pop("WORLD_SIZE", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args + ["--no-cpu-baseline"], capture_output=True, text=True, env=e, timeout=timeout)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args + ["--full", "--no-cpu-baseline"], capture_output=True, text=True, env=e, timeout=timeout)     # (--full: the check of the last proof)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]; assert len(lines) == 1, r.stdout[-500:]; return json.loads(lines[0])
 

@@ -16,6 +16,10 @@ class SplitMix64:
         l = [self.next() for _ in range(4)]; l[3] &= (1 << 61) - 1
         return l[0] | l[1] << 64 | l[2] << 128 | l[3] << 192
 
+def prover_rs(k):
+    """bench.py's fixed prover randomness (r, s) for statement k: two seeded full-width values below the group order (< 2^253), like the uniform ones a caller draws"""
+    g = SplitMix64(0x5EED7000 + k); return g.field(), g.field()
+
 def rev(b): return bytes(b)[::-1]
 def sha(b): return hashlib.sha256(b).digest()
 # all values below are BIG-ENDIAN byte strings as zktx.go holds them (common.Hash / common.Address); blob = reversed
