@@ -936,6 +936,8 @@ int zkgpu_test_verify_schedule(const char *vk_path, const char *proof_hex, const
       } res = verify_by_schedule_on_host(*vk, (const Fe32 *)inputs, n_inputs, p, stats) ? 1 : 0; return ZKGPU_OK; }); return rc == ZKGPU_OK ? res : rc; }
 /* small verification calls taken by the key's GPU verifier / launches made for them (calls that meet share a launch) */
 int zkgpu_verify_counters(const char *vk_path, uint64_t out[2]) { return guarded([&] { if (!vk_path || !out) return ZKGPU_ERR_ARG; gpu_verifier_for_path(vk_path)->counters(out); return ZKGPU_OK; }); }
+/* test entry: small calls, launches for them, launches of the workgroup-per-proof branch (65 to ZK_VERIFY_WAVE_MAX proofs), launches of the lane-per-proof branch */
+int zkgpu_verify_path_counters(const char *vk_path, uint64_t out[4]) { return guarded([&] { if (!vk_path || !out) return ZKGPU_ERR_ARG; gpu_verifier_for_path(vk_path)->path_counters(out); return ZKGPU_OK; }); }
 /* test entry (GPU): kernel K9's values after every `every`-th round of its schedule against the host model of the same limb arithmetic.  out[0] = first differing round or -1,
  * out[1] = the slot, out[2] = the kernel's verdict (1 accept, 0 reject, 2 handed back) */
 int zkgpu_test_verify_trace(const char *vk_path, const char *proof_hex, const uint8_t *inputs, size_t n_inputs, uint32_t every, long out[3]) { return guarded([&] {

@@ -124,6 +124,7 @@ class BatchVerifier {
   ~BatchVerifier();
   size_t num_inputs() const; size_t program_length() const;
   void counters(uint64_t out[2]) const;   // small calls taken / launches made for them (calls that meet share a launch)
+  void path_counters(uint64_t out[4]) const;   // the two above, then launches of the large-batch branches: workgroup per proof, lane per proof
   // proofs_mont: n records of 256 bytes (A.x A.y | B.x.c0 B.x.c1 B.y.c0 B.y.c1 | C.x C.y, Montgomery); inputs: n * num_inputs() canonical field elements; ok[i]
   // = 1 accept / 0 reject
   void verify(const void *proofs_mont, const Fe32 *inputs_canonical, size_t n, uint8_t *ok);

@@ -88,6 +88,7 @@ struct BatchVerifier::Impl {
   int max_in_flight() const { return (int)ctxs.size(); }      // as many launches under way as there are streams (ZK_VERIFY_STREAMS, default 16)
   std::mutex cm; std::condition_variable ccv; std::vector<Pending *> open; size_t open_n = 0; bool open_led = false; int in_flight = 0;
   std::atomic<uint64_t> launches{0}, calls{0};
+  std::atomic<uint64_t> wave_launches{0}, lane_launches{0};                  // launches of the large-batch branches: workgroup per proof / lane per proof
   // layout of a context's staging area (host and device alike): proofs | inputs | -acc | verdicts
   size_t off_in() const {
     return CTX_CAP * sizeof(VerifyItem);
@@ -282,6 +283,9 @@ static void launch_sched(BatchVerifier::Impl &d, unsigned n, hipStream_t s, cons
 size_t BatchVerifier::num_inputs() const { return impl->n_inputs; }
 size_t BatchVerifier::program_length() const { return impl->prog_len; }
 void BatchVerifier::counters(uint64_t out[2]) const { out[0] = impl->calls.load(); out[1] = impl->launches.load(); }
+void BatchVerifier::path_counters(uint64_t out[4]) const {
+  out[0] = impl->calls.load(); out[1] = impl->launches.load(); out[2] = impl->wave_launches.load(); out[3] = impl->lane_launches.load();
+}
 // test entry: ONE proof through the kernels with the values of every `every`-th round written out; nacc_out: the 96 bytes the accumulation kernel handed to the
 // schedule kernel (x w, -y w, w; Montgomery)
 uint8_t BatchVerifier::trace(const void *proof_mont, const Fe32 *inputs_canonical, uint32_t every, std::vector<uint32_t> &values, uint8_t nacc_out[96]) {
@@ -353,6 +357,7 @@ void BatchVerifier::verify(const void *proofs_mont, const Fe32 *inputs_canonical
   std::lock_guard<std::mutex> lk(d.big);
   DevArr<VerifyItem> items(n); DevBuf<Fe32> in(n * d.n_inputs + 1); DevArr<Affine<Fq>> acc(n); DevBuf<uint8_t> out(n);
   items.upload((const VerifyItem *)proofs_mont, n); if (d.n_inputs) in.upload(inputs_canonical, n * d.n_inputs);
+  HIP_CHECK(hipMemsetAsync(out.get(), 0xff, n, s));                         // (as in the small contexts: a verdict that never arrives is not read as one)
   Stage st("verify.batch");
   // up to WAVE_MAX proofs: one workgroup each (a proof's latency is the schedule's ~900 rounds; two workgroups share a CU: 0.9 ms for 256 proofs, 1.7 ms for 512,
   // 24.5 ms for 8,192 — 330 K proofs/s); beyond that the lane-per-proof kernel, whose 26 ms floor is then amortised over more (profiles/r06_verify_batch.txt)
@@ -362,14 +367,16 @@ void BatchVerifier::verify(const void *proofs_mont, const Fe32 *inputs_canonical
         (uint32_t)d.n_inputs, (uint32_t)n, acc3.get());
     // (acc3 lives until the kernels are done)
     launch_sched(d, (unsigned)n, s, items.get(), acc3.get(), out.get());
-    HIP_CHECK(hipStreamSynchronize(s));
+    HIP_CHECK(hipStreamSynchronize(s)); d.wave_launches.fetch_add(1, std::memory_order_relaxed);
   } else {
     hipLaunchKernelGGL(k_verify_acc, dim3(cdiv(n, 64)), dim3(64), 0, s, (const Affine<Fq> *)d.tables.get(), d.ic0, (const Fr *)in.get(), (uint32_t)d.n_inputs,
         (uint32_t)n, acc.get());
     hipLaunchKernelGGL(k_verify_batch, dim3(cdiv(n, 64)), dim3(64), 0, s, d.prog.get(), items.get(), acc.get(), d.gamma.get(), d.delta.get(), d.frob.get(),
         d.alpha_beta.get(), d.K, (uint32_t)n, out.get());
+    HIP_CHECK(hipStreamSynchronize(s)); d.lane_launches.fetch_add(1, std::memory_order_relaxed);
   }
   HIP_CHECK(hipGetLastError()); out.download(ok, n);
+  for (size_t k = 0; k < n; k++) if (ok[k] > 2) throw GpuError("verify: a verdict did not arrive");
 }
 
 }  // namespace zk

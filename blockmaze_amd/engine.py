@@ -213,6 +213,9 @@ def general_path_repeats():
 def verify_counters(vk_path):
     """(small verification calls taken by the key's GPU verifier, launches made for them)"""
     out = (ctypes.c_uint64 * 2)(); _check(lib().zkgpu_verify_counters(vk_path.encode(), out)); return int(out[0]), int(out[1])
+def verify_path_counters(vk_path):
+    """(small calls, launches for them, launches of the workgroup-per-proof branch, launches of the lane-per-proof branch) of the key's GPU verifier"""
+    out = (ctypes.c_uint64 * 4)(); _check(lib().zkgpu_verify_path_counters(vk_path.encode(), out)); return tuple(int(x) for x in out)
 def verify_trace(vk_path, proof_hex, inputs, every=1):
     """kernel K9 on one proof with its values written out after every `every`-th round, compared with the host model of the same arithmetic:
     (first differing round or -1, slot, the kernel's verdict)"""

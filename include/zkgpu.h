@@ -159,6 +159,9 @@ int zkgpu_test_verify_schedule(const char *vk_path, const char *proof_hex, const
 /* out[0] = small verification calls (up to 64 proofs) taken by this key's GPU verifier, out[1] = kernel launches made for them: calls that meet — go-ethereum verifies
  * from many goroutines, one proof a call — share a launch */
 int zkgpu_verify_counters(const char *vk_path, uint64_t out[2]);
+/* test entry: out[0], out[1] as zkgpu_verify_counters; out[2] = launches of the large-batch workgroup-per-proof branch (65 to ZK_VERIFY_WAVE_MAX proofs, default
+ * 8,192), out[3] = launches of the lane-per-proof branch (more than ZK_VERIFY_WAVE_MAX proofs) */
+int zkgpu_verify_path_counters(const char *vk_path, uint64_t out[4]);
 /* test entry (needs a GPU): kernel K9's LDS values after every `every`-th round of its schedule against the host model of the same 29-bit limb arithmetic, on one proof.
  * out[0] = the first round whose values differ or -1, out[1] = the slot, out[2] = the kernel's verdict (1 accept, 0 reject, 2 handed back to the host verifier) */
 int zkgpu_test_verify_trace(const char *vk_path, const char *proof_hex, const uint8_t *inputs, size_t n_inputs, uint32_t every, long out[3]);

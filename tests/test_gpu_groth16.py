@@ -10,6 +10,7 @@ from oracle import pyoracle as o
 from blockmaze_amd import engine as e
 import workload as w
 import verify_mutations as vm
+import verify_crafted
 from conftest import record_leg
 
 pytestmark = pytest.mark.gpu
@@ -238,19 +239,11 @@ def test_gpu_verifier_values_equal_the_host_model_round_by_round(golden_dir, nam
 
 @pytest.mark.parametrize("name", ["groth16_small", "groth16_step"])
 def test_batched_gpu_verifier_matches_host_verifier(golden_dir, name):
-    """K9: one lane per proof.  A batch mixing the reference prover's proof, fresh proofs, tampered proofs (each coordinate), wrong public inputs, the
+    """K9's large-batch branch: one workgroup per proof.  A batch mixing the reference prover's proof, fresh proofs, tampered proofs (each coordinate), wrong public inputs, the
     default proof and garbage must be decided exactly like the host verifier (which is pinned against libsnark's verifier and GT values)."""
     d = os.path.join(golden_dir, name); meta = json.load(open(os.path.join(d, "meta.json"))); z = o.load_witness(os.path.join(d, "wit.bin")); vk = os.path.join(d, "vk.txt")
     inputs = o.from_arr(z[:meta["n_inputs"]]); p = e.Prover(os.path.join(d, "pk.txt")); good = [meta["proof"]] + [p.prove(z) for _ in range(3)]; p.close()
-    proofs, ins = [], []
-    for g in good: proofs.append(g); ins.append(inputs)
-    for k in range(8):                                                                   # one flipped hex digit in each of the 8 coordinates
-        g = good[k % len(good)]; pos = 64 * k + 37; proofs.append(g[:pos] + ("0" if g[pos] != "0" else "1") + g[pos + 1:]); ins.append(inputs)
-    for j in range(len(inputs)): bad = list(inputs); bad[j] = (bad[j] + 1) % o.R_MOD; proofs.append(good[0]); ins.append(bad)
-    proofs.append(good[1]); ins.append([0] * len(inputs))
-    proofs.append("0" * 512); ins.append(inputs)                                          # all-zero record: (0,0) is off-curve
-    proofs.append("zz" + good[0][2:]); ins.append(inputs)                                 # not hex
-    proofs.append(good[2][:128] + good[3][128:]); ins.append(inputs)                      # A of one valid proof with B, C of another
+    proofs, ins = verify_crafted.mixed_batch(good, inputs)
     got = e.verify_batch(vk, proofs, ins); exp = [e.verify(vk, pr, x) for pr, x in zip(proofs, ins)]
     assert got == exp and got[:len(good)] == [True] * len(good) and not any(got[len(good):])
     # ... and like the ORACLE's verifier (checker code pinned against libsnark's verifier and GT values in test_oracle_golden.py), wherever the record is 512 hex digits of a
@@ -326,14 +319,7 @@ def test_gpu_verifier_random_curve_points_match_host(golden_dir):
     random public inputs — shuffled among 24 valid proofs with fresh (r, s): every verdict must be the host verifier's, in one launch and record by record"""
     d = os.path.join(golden_dir, "groth16_small"); meta = json.load(open(os.path.join(d, "meta.json"))); z = o.load_witness(os.path.join(d, "wit.bin")); vk = os.path.join(d, "vk.txt")
     inputs = o.from_arr(z[:meta["n_inputs"]]); p = e.Prover(os.path.join(d, "pk.txt")); good = [p.prove(z) for _ in range(24)]; p.close()
-    g = o.SplitMix64(2903); G1, G2 = o.g1_gen(), o.g2_gen(); rnd = lambda: 1 + g.next() % (o.R_MOD - 1)
-    def hexof(A, B, C): return o.proof_hex(o.to_arr([A[0], A[1], B[0][0], B[0][1], B[1][0], B[1][1], C[0], C[1]]).reshape(-1))
-    cases = [(pr, inputs) for pr in good]
-    for _ in range(120): cases.append((hexof(o.g1_op("mul", G1, k=rnd()), o.g2_op("mul", G2, k=rnd()), o.g1_op("mul", G1, k=rnd())), [rnd() for _ in inputs] if g.next() & 1 else inputs))
-    for _ in range(40): cases.append((good[g.next() % 24], [rnd() for _ in inputs]))            # a valid proof under random inputs
-    order = list(range(len(cases)))
-    for i in range(len(order) - 1, 0, -1): j = g.next() % (i + 1); order[i], order[j] = order[j], order[i]
-    cases = [cases[i] for i in order]; proofs = [c[0] for c in cases]; ins = [c[1] for c in cases]
+    proofs, ins = verify_crafted.random_curve_batch(good, inputs)
     got = e.verify_batch(vk, proofs, ins); exp = [e.verify(vk, pr, x) for pr, x in zip(proofs, ins)]
     assert got == exp and sum(got) == 24
     for pr, x, v in list(zip(proofs, ins, got))[:40]: assert e.verify_batch(vk, [pr], [x]) == [v]       # ... and one record per launch

@@ -19,19 +19,7 @@ def sha(x): import hashlib; return hashlib.sha256(repr(x).encode()).hexdigest()
 
 def H(x): return int(x, 16)
 
-def g1_bytes(P):
-    """compressed key-file encoding (alt_bn128_g1.cpp:404-418 under BINARY_OUTPUT / MONTGOMERY_OUTPUT): '0'|'1' is_zero, 32 bytes of Montgomery X (LE), '0'|'1' lsb of canonical Y"""
-    if P is None: return b"1" + bytes(32) + b"1"
-    return b"0" + o.to_mont(o.FQ, [P[0]])[0].to_bytes(32, "little") + (b"1" if P[1] & 1 else b"0")
-def g2_bytes(Q):
-    if Q is None: return b"1" + bytes(64) + b"1"
-    (x0, x1), (y0, y1) = Q; m = o.to_mont(o.FQ, [x0, x1]); return b"0" + m[0].to_bytes(32, "little") + m[1].to_bytes(32, "little") + (b"1" if y0 & 1 else b"0")
-def write_vk(path, gt12, gamma, delta, ic):
-    """r1cs_gg_ppzksnark.tcc:100-108 + accumulation_vector.tcc:63-69"""
-    n = len(ic) - 1; b = " ".join(str(c) for c in gt12).encode() + b"\n" + g2_bytes(gamma) + b"\n" + g2_bytes(delta) + b"\n" + g1_bytes(ic[0]) + b"\n"
-    b += b"%d\n%d\n" % (n, n) + b"".join(b"%d\n" % i for i in range(n)) + b"%d\n" % n + b"".join(g1_bytes(p) + b"\n" for p in ic[1:]) + b"\n\n"
-    open(path, "wb").write(b)
-def proof_hex(A, B, C): return o.proof_hex(o.to_arr([A[0], A[1], B[0][0], B[0][1], B[1][0], B[1][1], C[0], C[1]]).reshape(-1))
+from verify_crafted import g1_bytes, g2_bytes, write_vk, proof_hex  # noqa: F401  (the crafted-key writer, shared with tests/test_verifier_crafted_keys_cpu.py)
 
 @pytest.mark.parametrize("name", ["groth16_small", "groth16_step"])
 def test_reference_proofs_on_reference_keys(golden_dir, name):
