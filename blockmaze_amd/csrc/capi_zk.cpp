@@ -6,8 +6,10 @@
 //   * keys are looked up under /usr/local/prfKey/ (override: ZK_PRFKEY_DIR); unlike the reference they are parsed once
 //     and kept resident in HBM, re-read only when the file's size or mtime changes;
 //   * no exception, abort or signal handler ever crosses this boundary; calls may arrive concurrently on any thread.
+#include <sys/random.h>
 #include <sys/stat.h>
 #include <unistd.h>
+#include <cerrno>
 #include <chrono>
 #include <condition_variable>
 #include <cstdio>
@@ -25,6 +27,7 @@
 #include "../../include/zk_redeem.h"
 #include "../../include/zk_send.h"
 #include "../../include/zk_batch.h"
+#include "../../include/zk_block.h"
 #include "../../include/zkgpu.h"
 #include "blockmaze_circuits.hpp"
 #include "groth16.hpp"
@@ -64,7 +67,8 @@ typedef std::vector<std::shared_ptr<ProverUnit>> UnitList;
 // lets go of its reference — a caller can therefore never see a destroyed unit or mutex, however the reload interleaves with proofs in flight.
 struct ProverSlot { FileStamp stamp; std::vector<std::shared_ptr<const UnitList>> units /* one list per device slot, built on first use */;
     std::vector<uint8_t> building /* a caller is loading this device's pool */; std::atomic<unsigned> next{0}; };
-struct VkSlot { FileStamp stamp; std::shared_ptr<PreparedVerifyingKey> vk; std::shared_ptr<BatchVerifier> gpu; };
+struct VkSlot { FileStamp stamp; std::shared_ptr<PreparedVerifyingKey> vk; std::shared_ptr<BatchVerifier> gpu;
+  std::shared_ptr<BlockVerifier> block; int rlc_ok = -1 /* the key's check for the block equation (rlc_key_ok): -1 not made yet */; };
 std::mutex g_cache_mutex; std::map<std::string, ProverSlot> g_provers; std::map<std::string, VkSlot> g_vks;
 
 std::unique_ptr<Circuit> make_circuit(CircuitKind k, bool emit) {
@@ -176,7 +180,7 @@ HeldUnit acquire_prover(CircuitKind k) {
 std::shared_ptr<PreparedVerifyingKey> vk_for_path(const std::string &path) {
   FileStamp st; if (!stamp_of(path, st)) throw std::runtime_error("verification key not found: " + path);
   std::lock_guard<std::mutex> lk(g_cache_mutex); VkSlot &slot = g_vks[path];
-  if (!slot.vk || !(slot.stamp == st)) { slot.vk = prepare_verifying_key(load_verifying_key(path)); slot.gpu.reset(); slot.stamp = st; }
+  if (!slot.vk || !(slot.stamp == st)) { slot.vk = prepare_verifying_key(load_verifying_key(path)); slot.gpu.reset(); slot.block.reset(); slot.rlc_ok = -1; slot.stamp = st; }
   return slot.vk;
 }
 std::shared_ptr<PreparedVerifyingKey> vk_for(CircuitKind k) { return vk_for_path(key_path(k, false)); }
@@ -990,6 +994,169 @@ int verifyBatch(const zk_verify_item *items, int n, unsigned char *ok) {
   catch (const std::exception &e) {
     zkgpu_set_error(e.what());
     fprintf(stderr, "libzkgpu: verifyBatch: %s\n", e.what());
+    for (int i = 0; i < n; i++) ok[i] = 0;
+    return -1;
+  }
+  catch (...) { for (int i = 0; i < n; i++) ok[i] = 0; return -1; }
+}
+
+// ---- the randomized block check (DESIGN.md "Block verification"; include/zk_block.h, zkgpu_verify_batch_rlc) ------------------------------------------------
+// One equation over all records of a call, FE(prod_i Miller(A_i, B_i)^{r_i} * Miller(-S_acc, gamma) * Miller(-S_C, delta)) == alpha_g1_beta_g2^{sum r_i}; when it
+// fails, or cannot be formed, every record is decided by the per-proof path and the verdicts are verifyBatch's.  Below RLC_MIN_RECORDS records (of a call, or
+// of one kind in a block) the per-proof path is taken at once: the lane-per-record kernel has a floor of about 15 ms that the per-proof kernel K9 undercuts on
+// small calls.  profiles/verify_block.txt: in device time the crossover lies between 4,096 records (K9 12.4 ms, block kernels 15.1) and 6,144 (18.4 against
+// 15.2); the equation's host work (S_acc, the closing Miller loops and final exponentiation) adds a few ms a call, and 8,192 is the smallest measured size at
+// which the call is faster in device and in wall time alike — a conservative bound.
+static const size_t RLC_MIN_RECORDS = 8192;
+static std::atomic<uint64_t> g_rlc_passed{0}, g_rlc_failed{0}, g_rlc_per_proof{0};
+namespace {
+// the key's device half of the check, null if the key fails rlc_key_ok (its calls are then decided proof by proof)
+static std::shared_ptr<BlockVerifier> block_verifier_for_path(const std::string &path) {
+  std::shared_ptr<PreparedVerifyingKey> vk = vk_for_path(path); std::lock_guard<std::mutex> lk(g_cache_mutex); VkSlot &slot = g_vks[path];
+  if (slot.rlc_ok < 0) slot.rlc_ok = rlc_key_ok(*vk) ? 1 : 0;
+  if (slot.rlc_ok == 1 && !slot.block) slot.block = std::shared_ptr<BlockVerifier>(make_block_verifier(*vk).release());
+  return slot.rlc_ok == 1 ? slot.block : nullptr;
+}
+static bool is_zero_weight(const uint8_t *w) { for (int k = 0; k < 16; k++) if (w[k]) return false; return true; }
+static void random_bytes(uint8_t *p, size_t n) {
+  for (size_t got = 0; got < n;) { const ssize_t k = getrandom(p + got, n - got, 0); if (k < 0) { if (errno == EINTR) continue; throw std::runtime_error("getrandom failed"); } got += (size_t)k; }
+}
+// r_i uniform in [1, 2^128) from getrandom(2): a draw of 0 is drawn again
+static void fresh_weights(uint8_t *w, size_t n) {
+  random_bytes(w, 16 * n);
+  for (size_t i = 0; i < n; i++) while (is_zero_weight(w + 16 * i)) random_bytes(w + 16 * i, 16);
+}
+// one key's share of the equation: the device half, then S_acc on the host.  false: this key cannot take part (it fails rlc_key_ok).  in_eq: records flagged 1
+struct RlcPart { std::vector<uint8_t> flags; host::HFq12 prod; host::HG1 s_acc, s_c; uint64_t s[4]; size_t in_eq = 0; };
+static bool rlc_part(const std::string &path, const Proof *ps, const Fe32 *inputs, size_t ni, size_t m, const uint8_t *w, bool lock, RlcPart &out) {
+  std::unique_lock<std::mutex> gl(g_gpu_mutex, std::defer_lock); if (lock) gl.lock();
+  std::shared_ptr<BlockVerifier> bv = block_verifier_for_path(path); if (!bv) return false;
+  if (bv->num_inputs() != ni) throw std::runtime_error("block verify: input count");
+  out.flags.assign(m, 0); bv->run(ps, inputs, w, m, out.flags.data(), out.prod, out.s_c); if (lock) gl.unlock();
+  out.s_acc = rlc_acc_sum(*vk_for_path(path), inputs, ni, w, out.flags.data(), m, out.s);
+  out.in_eq = 0; for (size_t i = 0; i < m; i++) out.in_eq += out.flags[i] == 1;
+  return true;
+}
+// verdicts of a part whose equation held: the screen's rejections, the per-proof host verifier for an accumulator at infinity
+static void decide_from_flags(const std::string &path, const RlcPart &p, const Proof *ps, const uint8_t *parsed, const Fe32 *inputs, size_t ni, size_t m, uint8_t *res) {
+  for (size_t i = 0; i < m; i++) res[i] = !parsed[i] ? 0 : p.flags[i] == 1 ? 1 : p.flags[i] == 2 ? (verify_proof(*vk_for_path(path), inputs + i * ni, ni, ps[i]) ? 1 : 0) : 0;
+}
+static void gt_bytes(const host::HFq12 &g, uint8_t out[384]) {
+  host::HFq c[12]; static_assert(sizeof(c) == sizeof(g), "GT layout"); memcpy(c, &g, sizeof c);
+  for (int k = 0; k < 12; k++) { const host::HFq v = c[k].from_mont(); memcpy(out + 32 * k, v.l, 32); }
+}
+// a call's records parsed as zkgpu_verify_batch parses them
+static void parse_records(const char *proofs_hex, size_t n, std::vector<Proof> &ps, std::vector<uint8_t> &parsed) {
+  ps.assign(n, Proof()); parsed.assign(n, 0);
+  for (size_t i = 0; i < n; i++) {
+    parsed[i] = strnlen(proofs_hex + 512 * i, 512) == 512 && proof_from_hex(proofs_hex + 512 * i, ps[i]);
+    if (!parsed[i]) memset(&ps[i], 0, sizeof(Proof));
+  }
+}
+static bool weights_from(const uint8_t *given, size_t n, std::vector<uint8_t> &w) {
+  w.assign(16 * n, 0); if (!given) { fresh_weights(w.data(), n); return true; }
+  memcpy(w.data(), given, 16 * n); for (size_t i = 0; i < n; i++) if (is_zero_weight(&w[16 * i])) return false;
+  return true;
+}
+}  // namespace
+
+int zkgpu_verify_batch_rlc(const char *vk_path, const char *proofs_hex, const uint8_t *inputs, size_t n_inputs, size_t n, const uint8_t *weights, uint8_t *ok,
+    uint32_t *by_equation) { return guarded([&] {
+  if (!vk_path || (!proofs_hex && n) || !ok) return ZKGPU_ERR_ARG;
+  if (by_equation) *by_equation = 0;
+  std::vector<uint8_t> w; if (!weights_from(weights, n, w)) { zkgpu_set_error("a weight is 0"); return ZKGPU_ERR_ARG; }
+  std::shared_ptr<BatchVerifier> v = gpu_verifier_for_path(vk_path); const Fe32 *in = (const Fe32 *)inputs;
+  if (v->num_inputs() != n_inputs) { for (size_t i = 0; i < n; i++) ok[i] = 0; g_rlc_per_proof.fetch_add(1); return ZKGPU_OK; }   // strong IC
+  std::vector<Proof> ps; std::vector<uint8_t> parsed; parse_records(proofs_hex, n, ps, parsed);
+  bool decided = false;
+  if (n >= RLC_MIN_RECORDS) {
+    try {
+      RlcPart p;
+      if (rlc_part(vk_path, ps.data(), in, n_inputs, n, w.data(), false, p) && p.in_eq && !p.s_acc.is_inf() && !p.s_c.is_inf()) {
+        const bool pass = host::final_exponentiation(rlc_lhs(*vk_for_path(vk_path), p.prod, p.s_acc, p.s_c)) == rlc_rhs(*vk_for_path(vk_path), p.s);
+        (pass ? g_rlc_passed : g_rlc_failed).fetch_add(1);
+        if (pass) { decide_from_flags(vk_path, p, ps.data(), parsed.data(), in, n_inputs, n, ok); decided = true; }
+      }
+    } catch (const std::exception &e) { fprintf(stderr, "libzkgpu: block check failed (%s); deciding %zu proof(s) one by one\n", e.what(), n); }
+  }
+  if (!decided) {                                                                  // the per-proof path: exactly zkgpu_verify_batch
+    g_rlc_per_proof.fetch_add(1); v->verify(ps.data(), in, n, ok);
+    for (size_t i = 0; i < n; i++) { if (!parsed[i]) ok[i] = 0; else if (ok[i] == 2) ok[i] = verify_proof(*vk_for_path(vk_path), in + i * n_inputs, n_inputs, ps[i]) ? 1 : 0; }
+  }
+  if (by_equation) *by_equation = decided ? 1 : 0;
+  return ZKGPU_OK; }); }
+// test entries: the left-hand side's GT value FE(...) and whether it equals the right-hand side, for given weights, on the device (whatever the record count) or on
+// the host.  Points at infinity contribute 1 (no fallback here).  Returns 1 / 0, or an error
+int zkgpu_test_verify_rlc_device(const char *vk_path, const char *proofs_hex, const uint8_t *inputs, size_t n_inputs, size_t n, const uint8_t *weights, uint8_t *gt) {
+  int res = 0; int rc = guarded([&] {
+    if (!vk_path || !proofs_hex || !n) return ZKGPU_ERR_ARG;
+    std::vector<uint8_t> w; if (!weights_from(weights, n, w)) return ZKGPU_ERR_ARG;
+    std::vector<Proof> ps; std::vector<uint8_t> parsed; parse_records(proofs_hex, n, ps, parsed); RlcPart p;
+    if (!rlc_part(vk_path, ps.data(), (const Fe32 *)inputs, n_inputs, n, w.data(), false, p)) { zkgpu_set_error("the key fails the subgroup checks of the block equation"); return ZKGPU_ERR_ARG; }
+    const host::HFq12 g = host::final_exponentiation(rlc_lhs(*vk_for_path(vk_path), p.prod, p.s_acc, p.s_c)); if (gt) gt_bytes(g, gt);
+    res = g == rlc_rhs(*vk_for_path(vk_path), p.s) ? 1 : 0; return ZKGPU_OK; });
+  return rc == ZKGPU_OK ? res : rc; }
+int zkgpu_test_verify_rlc_host(const char *vk_path, const char *proofs_hex, const uint8_t *inputs, size_t n_inputs, size_t n, const uint8_t *weights, uint8_t *gt) {
+  int res = 0; int rc = guarded_host([&] {
+    if (!vk_path || !proofs_hex || !n) return ZKGPU_ERR_ARG;
+    std::vector<uint8_t> w; if (!weights_from(weights, n, w)) return ZKGPU_ERR_ARG;
+    std::shared_ptr<PreparedVerifyingKey> vk = vk_for_path(vk_path); if (vk->vk.IC.size() != n_inputs + 1) return ZKGPU_ERR_ARG;
+    std::vector<Proof> ps; std::vector<uint8_t> parsed; parse_records(proofs_hex, n, ps, parsed); host::HFq12 g;
+    res = rlc_equation_host(*vk, ps.data(), parsed.data(), (const Fe32 *)inputs, n_inputs, n, w.data(), &g, nullptr) ? 1 : 0; if (gt) gt_bytes(g, gt); return ZKGPU_OK; });
+  return rc == ZKGPU_OK ? res : rc; }
+int zkgpu_verify_rlc_counters(uint64_t out[3]) {
+  if (!out) return ZKGPU_ERR_ARG;
+  out[0] = g_rlc_passed.load(); out[1] = g_rlc_failed.load(); out[2] = g_rlc_per_proof.load(); return ZKGPU_OK;
+}
+
+// verifyBlock (include/zk_block.h): the records grouped by kind as verifyBatch groups them.  A kind with at least RLC_MIN_RECORDS records (and the right input
+// count) takes part in the block's equation: its left-hand factor goes into one Fq12 value, its alpha_beta^s into one right-hand side, and the block takes ONE
+// final exponentiation.  Every other kind — a small one, one whose key fails rlc_key_ok, one with no record in the equation or a sum at infinity — goes through
+// verify_group exactly as in verifyBatch, and so does every kind of the equation if the equation fails or a device step throws.
+int verifyBlock(const zk_verify_item *items, int n, unsigned char *ok) {
+  if (n < 0 || (n && (!items || !ok))) return -1;
+  try {
+    struct Group { CircuitKind kind; std::string path; std::vector<int> idx; std::vector<Proof> ps; std::vector<uint8_t> parsed, res; std::vector<Fe32> inputs; size_t ni = 0;
+      RlcPart part; bool in_eq = false, decided = false; };
+    std::vector<Group> groups; std::vector<int> idx[4];
+    for (int i = 0; i < n; i++) { ok[i] = 0; if (items[i].kind >= 0 && items[i].kind <= 3) idx[items[i].kind].push_back(i); }
+    for (int k = 0; k < 4; k++) { if (idx[k].empty()) continue; Group g; g.kind = (CircuitKind)k; g.path = key_path(g.kind, false); g.idx = idx[k]; const size_t m = g.idx.size();
+      g.ps.resize(m); g.parsed.resize(m); g.res.assign(m, 0);
+      for (size_t j = 0; j < m; j++) {
+        const zk_verify_item &it = items[g.idx[j]];
+        g.parsed[j] = it.proof && strnlen(it.proof, 512) == 512 && proof_from_hex(it.proof, g.ps[j]);
+        if (!g.parsed[j]) memset(&g.ps[j], 0, sizeof(Proof));
+        std::vector<Fe32> in = pack_public_bits(public_bits(g.kind, it.args, it.value_s)); g.ni = in.size(); g.inputs.insert(g.inputs.end(), in.begin(), in.end()); }
+      groups.push_back(std::move(g)); }
+    bool any_eq = false;
+    if (gpu_available()) {
+      try {
+        host::HFq12 lhs = host::HFq12::one(), rhs = host::HFq12::one();
+        for (Group &g : groups) {
+          const size_t m = g.idx.size(); if (m < RLC_MIN_RECORDS) continue;
+          std::shared_ptr<PreparedVerifyingKey> vk = vk_for_path(g.path); if (vk->vk.IC.size() != g.ni + 1) continue;   // (strong IC: verify_group rejects the group)
+          std::vector<uint8_t> w(16 * m); fresh_weights(w.data(), m);
+          if (!rlc_part(g.path, g.ps.data(), g.inputs.data(), g.ni, m, w.data(), true, g.part) || !g.part.in_eq || g.part.s_acc.is_inf() || g.part.s_c.is_inf()) continue;
+          lhs = lhs * rlc_lhs(*vk, g.part.prod, g.part.s_acc, g.part.s_c); rhs = rhs * rlc_rhs(*vk, g.part.s); g.in_eq = true; any_eq = true;
+        }
+        if (any_eq) {
+          const bool pass = host::final_exponentiation(lhs) == rhs; (pass ? g_rlc_passed : g_rlc_failed).fetch_add(1);
+          if (pass) { for (Group &g : groups) if (g.in_eq) { decide_from_flags(g.path, g.part, g.ps.data(), g.parsed.data(), g.inputs.data(), g.ni, g.idx.size(), g.res.data()); g.decided = true; } }
+          else any_eq = false;
+        }
+      } catch (const std::exception &e) {
+        fprintf(stderr, "libzkgpu: verifyBlock: block check failed (%s); deciding proof by proof\n", e.what());
+        any_eq = false; for (Group &g : groups) g.decided = false;
+      }
+    }
+    if (!any_eq) g_rlc_per_proof.fetch_add(1);
+    for (Group &g : groups) if (!g.decided) verify_group(g.kind, g.ps.data(), g.parsed.data(), g.inputs.data(), g.ni, g.idx.size(), g.res.data());
+    int accepted = 0;
+    for (Group &g : groups) for (size_t j = 0; j < g.idx.size(); j++) { ok[g.idx[j]] = g.res[j]; accepted += g.res[j]; }
+    return accepted;
+  }
+  catch (const std::exception &e) {
+    zkgpu_set_error(e.what()); fprintf(stderr, "libzkgpu: verifyBlock: %s\n", e.what());
     for (int i = 0; i < n; i++) ok[i] = 0;
     return -1;
   }

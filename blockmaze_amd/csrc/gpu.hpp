@@ -131,6 +131,18 @@ class BatchVerifier {
   uint8_t trace(const void *proof_mont, const Fe32 *inputs_canonical, uint32_t every, std::vector<uint32_t> &values, uint8_t nacc_out[96]);   // tests (gpu_verify.hip)
   struct Impl; std::unique_ptr<Impl> impl;
 };
+// The device half of the randomized block check (gpu_verify_block.hip): one lane per record.  ic_x / ic_y: the prepared key's window tables of IC[1..]
+// ([j][w*255 + d-1], affine Montgomery, (0,0) = infinity).
+class BlockVerifier {
+ public:
+  BlockVerifier(const host::HFq *ic_x, const host::HFq *ic_y, size_t n_inputs, const G1AffineRaw &ic0);
+  ~BlockVerifier();
+  size_t num_inputs() const;
+  // weights: n x 16 bytes (little-endian 128-bit r_i).  flags[i]: 1 in the equation, 0 rejected by the screen, 2 input accumulator at infinity.  prod = the product of
+  // Miller(A_i, B_i)^{r_i}, sum_c = the sum of r_i C_i, both over the records flagged 1
+  void run(const void *proofs_mont, const Fe32 *inputs_canonical, const uint8_t *weights, size_t n, uint8_t *flags, host::HFq12 &prod, host::HG1 &sum_c);
+  struct Impl; std::unique_ptr<Impl> impl;
+};
 
 // Evaluation domain of size m = 2^k or 2^k + 2^r (libfqfft get_evaluation_domain, get_evaluation_domain.tcc:33-52) with
 // its twiddle / coset tables resident in HBM.

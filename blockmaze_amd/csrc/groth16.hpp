@@ -120,6 +120,18 @@ long verify_schedule_trace_on_device(BatchVerifier &bv, const PreparedVerifyingK
     uint32_t *bad_slot, uint8_t *device_ok);
 // the same decision for n proofs at once on the GPU (kernel K9): one BatchVerifier per verifying key
 std::unique_ptr<BatchVerifier> make_batch_verifier(const VerifyingKeyHost &vk);
+// ---- the randomized block check (DESIGN.md "Block verification"; groth16_verifier.cpp).  weights: 16 bytes (little-endian r_i) per record; flags as
+// BlockVerifier::run writes them (1 in the equation, 0 rejected by the screen, 2 input accumulator at infinity)
+bool rlc_key_ok(const PreparedVerifyingKey &pvk);    // [r]gamma = [r]delta = O and alpha_g1_beta_g2^r = 1: the key may be checked with the equation
+// S_acc = s IC[0] + sum_j (sum_i r_i x_ij) IC[j+1] over the records flagged 1; s_out = s mod r, canonical
+host::HG1 rlc_acc_sum(const PreparedVerifyingKey &pvk, const Fe32 *inputs, size_t ni, const uint8_t *weights, const uint8_t *flags, size_t n, uint64_t s_out[4]);
+// prod * Miller(-S_acc, gamma) * Miller(-S_C, delta), a point at infinity contributing 1 (before the final exponentiation)
+host::HFq12 rlc_lhs(const PreparedVerifyingKey &pvk, const host::HFq12 &prod, const host::HG1 &s_acc, const host::HG1 &s_c);
+host::HFq12 rlc_rhs(const PreparedVerifyingKey &pvk, const uint64_t s[4]);   // alpha_g1_beta_g2^s
+// the whole equation on the host (the model the device path is tested against): returns FE(lhs) == rhs; gt = FE(lhs); flags_out optional
+bool rlc_equation_host(const PreparedVerifyingKey &pvk, const Proof *ps, const uint8_t *parsed, const Fe32 *inputs, size_t ni, size_t n, const uint8_t *weights,
+    host::HFq12 *gt, uint8_t *flags_out);
+std::unique_ptr<BlockVerifier> make_block_verifier(const PreparedVerifyingKey &pvk);
 static_assert(sizeof(Proof) == 256, "proof record");
 
 // proof <-> the 512-hex-character form of the cgo wrappers (sendcgo.cpp:113-188, :388-448)

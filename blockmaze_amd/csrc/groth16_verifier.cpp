@@ -155,6 +155,70 @@ std::unique_ptr<BatchVerifier> make_batch_verifier(const VerifyingKeyHost &vk) {
   return std::unique_ptr<BatchVerifier>(new BatchVerifier(vk.alpha_g1_beta_g2, vk.gamma_g2, vk.delta_g2, vk.IC.data(), vk.IC.size()));
 }
 
+// ---- the randomized block check (DESIGN.md "Block verification"): host halves and the host model --------------------------------------------------------------
+static void r_limbs(uint64_t r[4]) { for (int i = 0; i < 4; i++) r[i] = HFr::mod(i); }
+static HFq12 fq12_pow(const HFq12 &b, const uint64_t *e, int limbs) {
+  HFq12 r = HFq12::one(); bool found = false;
+  for (int i = limbs * 64 - 1; i >= 0; i--) { if (found) r = r.sqr(); if ((e[i / 64] >> (i % 64)) & 1) { found = true; r = r * b; } }
+  return r;
+}
+bool rlc_key_ok(const PreparedVerifyingKey &pvk) {
+  uint64_t r[4]; r_limbs(r); const VerifyingKeyHost &vk = pvk.vk;
+  return g2_of(vk.gamma_g2).mul(r).is_inf() && g2_of(vk.delta_g2).mul(r).is_inf() && fq12_pow(vk.alpha_g1_beta_g2, r, 4) == HFq12::one();
+}
+host::HG1 rlc_acc_sum(const PreparedVerifyingKey &pvk, const Fe32 *inputs, size_t ni, const uint8_t *weights, const uint8_t *flags, size_t n, uint64_t s_out[4]) {
+  const VerifyingKeyHost &vk = pvk.vk; if (vk.IC.size() != ni + 1) throw std::runtime_error("block verify: input count");
+  // the integers s = sum r_i and c_j = sum r_i x_ij in 7 limbs each (128 + 256 bits a product, fewer than 2^31 records), reduced modulo r once at the end
+  std::vector<uint64_t> acc((ni + 1) * 7, 0);
+  auto add_at = [](uint64_t *a, int k, u128 v) { for (; v && k < 7; k++) { const u128 s = (u128)a[k] + (uint64_t)v; a[k] = (uint64_t)s; v = (v >> 64) + (s >> 64); } };
+  for (size_t i = 0; i < n; i++) {
+    if (flags[i] != 1) continue;
+    uint64_t w[2]; memcpy(w, weights + 16 * i, 16); add_at(&acc[0], 0, w[0]); add_at(&acc[0], 1, w[1]);
+    for (size_t j = 0; j < ni; j++) { uint64_t x[4]; memcpy(x, &inputs[i * ni + j], 32);
+      for (int a = 0; a < 2; a++) for (int b = 0; b < 4; b++) add_at(&acc[(j + 1) * 7], a + b, (u128)w[a] * x[b]); }
+  }
+  const HFr two64 = HFr::from_u64(1ull << 32) * HFr::from_u64(1ull << 32);
+  auto reduce = [&](const uint64_t *a, uint64_t out[4]) { HFr v = HFr::zero(); for (int k = 6; k >= 0; k--) v = v * two64 + HFr::from_u64(a[k]); v = v.from_mont(); memcpy(out, v.l, 32); };
+  reduce(&acc[0], s_out); HG1 S = g1_of(vk.IC[0]).mul(s_out);
+  for (size_t j = 0; j < ni; j++) { uint64_t c[4]; reduce(&acc[(j + 1) * 7], c); if (!is_zero_raw(&vk.IC[j + 1], sizeof(G1AffineRaw))) S = S.add(g1_of(vk.IC[j + 1]).mul(c)); }
+  return S;
+}
+host::HFq12 rlc_lhs(const PreparedVerifyingKey &pvk, const host::HFq12 &prod, const host::HG1 &s_acc, const host::HG1 &s_c) {
+  HFq12 m = prod; HFq x, y;
+  if (!s_acc.is_inf()) { s_acc.to_affine(x, y); m = m * miller_loop(x, y.neg(), pvk.gamma); }
+  if (!s_c.is_inf()) { s_c.to_affine(x, y); m = m * miller_loop(x, y.neg(), pvk.delta); }
+  return m;
+}
+host::HFq12 rlc_rhs(const PreparedVerifyingKey &pvk, const uint64_t s[4]) { return fq12_pow(pvk.vk.alpha_g1_beta_g2, s, 4); }
+// the screen of verify_proof: 0 rejected (not parsed, a point at infinity or off its curve), 2 input accumulator at infinity, 1 in the equation
+static uint8_t rlc_screen_host(const PreparedVerifyingKey &pvk, const Fe32 *inputs, size_t ni, const Proof &proof, bool parsed) {
+  if (!parsed || pvk.vk.IC.size() != ni + 1) return 0;
+  if (is_zero_raw(&proof.A, sizeof proof.A) || is_zero_raw(&proof.B, sizeof proof.B) || is_zero_raw(&proof.C, sizeof proof.C)) return 0;
+  if (!(g1_on_curve(fq_of(proof.A.x), fq_of(proof.A.y)) && g2_on_curve(fq2_of(proof.B.x0, proof.B.x1), fq2_of(proof.B.y0, proof.B.y1)) &&
+        g1_on_curve(fq_of(proof.C.x), fq_of(proof.C.y)))) return 0;
+  HG1 acc = g1_of(pvk.vk.IC[0]);
+  for (size_t j = 0; j < ni; j++) { const uint8_t *b = reinterpret_cast<const uint8_t *>(&inputs[j]);
+    for (int w = 0; w < 32; w++) if (b[w]) { const size_t k = j * 32 * 255 + (size_t)w * 255 + b[w] - 1;
+      if (!(pvk.ic_x[k].is_zero() && pvk.ic_y[k].is_zero())) acc = acc.add(HG1::from_affine(pvk.ic_x[k], pvk.ic_y[k])); } }
+  return acc.is_inf() ? 2 : 1;
+}
+bool rlc_equation_host(const PreparedVerifyingKey &pvk, const Proof *ps, const uint8_t *parsed, const Fe32 *inputs, size_t ni, size_t n, const uint8_t *weights,
+    host::HFq12 *gt, uint8_t *flags_out) {
+  std::vector<uint8_t> fl(n); HFq12 prod = HFq12::one(); HG1 sc = HG1::inf();
+  for (size_t i = 0; i < n; i++) {
+    fl[i] = rlc_screen_host(pvk, inputs + i * ni, ni, ps[i], parsed[i]); if (fl[i] != 1) continue;
+    uint64_t w[4] = {0, 0, 0, 0}; memcpy(w, weights + 16 * i, 16); const Proof &p = ps[i];
+    prod = prod * fq12_pow(miller_loop(fq_of(p.A.x), fq_of(p.A.y), precompute_g2(fq2_of(p.B.x0, p.B.x1), fq2_of(p.B.y0, p.B.y1))), w, 2);
+    sc = sc.add(g1_of(p.C).mul(w));
+  }
+  uint64_t s[4]; const HG1 sa = rlc_acc_sum(pvk, inputs, ni, weights, fl.data(), n, s);
+  const HFq12 g = final_exponentiation(rlc_lhs(pvk, prod, sa, sc)); if (gt) *gt = g; if (flags_out) memcpy(flags_out, fl.data(), n);
+  return g == rlc_rhs(pvk, s);
+}
+std::unique_ptr<BlockVerifier> make_block_verifier(const PreparedVerifyingKey &pvk) {
+  const size_t ni = pvk.vk.IC.size() - 1; return std::unique_ptr<BlockVerifier>(new BlockVerifier(pvk.ic_x.data(), pvk.ic_y.data(), ni, pvk.vk.IC[0]));
+}
+
 static void put_hex_fq(std::string &o, const Fe32 &mont) {
   HFq c = fq_of(mont).from_mont();
   static const char *d = "0123456789abcdef";

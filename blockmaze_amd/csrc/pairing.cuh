@@ -18,6 +18,7 @@
 #include "curve.cuh"
 #include "field29.cuh"
 #include "verify_sched.hpp"
+#include "pairing_types.cuh"
 
 namespace zk {
 
@@ -25,27 +26,8 @@ __device__ __forceinline__ Fq shfl_down_fq(const Fq &v, int delta) { Fq r;
 #pragma unroll
   for (int i = 0; i < 8; i++) r.l[i] = __shfl_down(v.l[i], delta, 64);
   return r; }
-struct Fq6 {
-  Fq2 c0, c1, c2;
-  static __device__ __forceinline__ Fq6 zero() { return {Fq2::zero(), Fq2::zero(), Fq2::zero()}; }
-  static __device__ __forceinline__ Fq6 one() { return {Fq2::one(), Fq2::zero(), Fq2::zero()}; }
-  friend __device__ __forceinline__ Fq6 operator+(const Fq6 &a, const Fq6 &b) { return {a.c0 + b.c0, a.c1 + b.c1, a.c2 + b.c2}; }
-  friend __device__ __forceinline__ Fq6 operator-(const Fq6 &a, const Fq6 &b) { return {a.c0 - b.c0, a.c1 - b.c1, a.c2 - b.c2}; }
-  __device__ __forceinline__ Fq6 neg() const { return {c0.neg(), c1.neg(), c2.neg()}; }
-  friend __device__ __forceinline__ Fq6 operator*(const Fq6 &a, const Fq6 &b) {   // Karatsuba, fp6_3over2.tcc:94-108
-    Fq2 aA = a.c0 * b.c0, bB = a.c1 * b.c1, cC = a.c2 * b.c2;
-    return {aA + ((a.c1 + a.c2) * (b.c1 + b.c2) - bB - cC).mul_xi(), (a.c0 + a.c1) * (b.c0 + b.c1) - aA - bB + cC.mul_xi(),
-        (a.c0 + a.c2) * (b.c0 + b.c2) - aA + bB - cC};
-  }
-  __device__ __forceinline__ Fq6 mul_by_v() const { return {c2.mul_xi(), c0, c1}; }
-  __device__ __forceinline__ bool operator==(const Fq6 &o) const { return c0 == o.c0 && c1 == o.c1 && c2 == o.c2; }
-};
-struct Fq12 { Fq6 c0, c1; __device__ __forceinline__ bool operator==(const Fq12 &o) const { return c0 == o.c0 && c1 == o.c1; } };
-
 struct FrobeniusDev { Fq2 fq6_c1[6], fq6_c2[6], fq12_c1[12], twist_mul_by_q_x, twist_mul_by_q_y; };   // same layout as host::FrobeniusTables
 struct EllCoeffsDev { Fq2 ell_0, ell_VW, ell_VV; };
-// Montgomery form, as parsed from the 512 hex characters
-struct VerifyItem { Affine<Fq> A; Affine<Fq2> B; Affine<Fq> C; };
 
 enum VmOp : uint32_t { VM_MUL = 0, VM_CONJ, VM_FROB, VM_INV, VM_ONE, VM_DBL, VM_ADD, VM_LINE, VM_END, VM_MUL024, VM_CYCSQR };
 __host__ __device__ inline uint32_t vm_ins(uint32_t op, uint32_t d, uint32_t a, uint32_t b) { return op | d << 8 | a << 16 | b << 24; }

@@ -195,6 +195,29 @@ def verify_batch(vk_path, proofs_hex, inputs):
         for j, v in enumerate(row): buf[32 * (i * ni + j):32 * (i * ni + j + 1)] = list(int(v).to_bytes(32, "little"))
     ok = (ctypes.c_uint8 * max(1, n))(); _check(lib().zkgpu_verify_batch(vk_path.encode(), blob, buf, ctypes.c_size_t(ni), ctypes.c_size_t(n), ok)); return [bool(ok[i]) for i in range(n)]
 
+def _batch_args(proofs_hex, inputs, weights):
+    n = len(proofs_hex); ni = len(inputs[0]) if n else 0; blob = "".join(proofs_hex).encode(); assert len(blob) == 512 * n
+    buf = b"".join(int(v).to_bytes(32, "little") for row in inputs for v in row); assert len(buf) == 32 * n * ni
+    wb = None if weights is None else b"".join(int(r).to_bytes(16, "little") for r in weights)
+    assert wb is None or len(wb) == 16 * n
+    return n, ni, blob, buf or b"\0", wb
+def verify_batch_rlc(vk_path, proofs_hex, inputs, weights=None):
+    """zkgpu_verify_batch_rlc: the verdicts of verify_batch by one randomized pairing-product check (weights: n ints in [1, 2^128), or None for fresh ones)
+    -> (list of n booleans, True if the equation decided the call)"""
+    n, ni, blob, buf, wb = _batch_args(proofs_hex, inputs, weights); ok = (ctypes.c_uint8 * max(1, n))(); by = ctypes.c_uint32(0)
+    _check(lib().zkgpu_verify_batch_rlc(vk_path.encode(), blob, buf, ctypes.c_size_t(ni), ctypes.c_size_t(n), wb, ok, ctypes.byref(by)))
+    return [bool(ok[i]) for i in range(n)], bool(by.value)
+def verify_rlc_equation(vk_path, proofs_hex, inputs, weights, device=False):
+    """the block equation for explicit weights, on the host model (no device) or through the device path -> (holds, 384-byte GT value of the left-hand side)"""
+    n, ni, blob, buf, wb = _batch_args(proofs_hex, inputs, weights); gt = (ctypes.c_uint8 * 384)()
+    f = lib().zkgpu_test_verify_rlc_device if device else lib().zkgpu_test_verify_rlc_host
+    rc = f(vk_path.encode(), blob, buf, ctypes.c_size_t(ni), ctypes.c_size_t(n), wb, gt)
+    if rc < 0: _check(rc)
+    return rc == 1, bytes(gt)
+def verify_rlc_counters():
+    """(block equations that held, equations that failed, calls decided proof by proof), process-wide"""
+    out = (ctypes.c_uint64 * 3)(); _check(lib().zkgpu_verify_rlc_counters(out)); return tuple(int(x) for x in out)
+
 def verify_schedule_on_host(vk_path, proof_hex, inputs):
     """the GPU verifier's operation schedule (csrc/verify_sched.hpp) interpreted on the host: (accept, {rounds, slots, products, linear_ops, constants, mul_waves, lin8_waves, lin1_waves}); needs no device"""
     buf = b"".join(int(x).to_bytes(32, "little") for x in inputs); st = (ctypes.c_uint32 * 8)()
@@ -260,6 +283,14 @@ class Zk:
             arr[i].kind = KIND[kind] if isinstance(kind, str) else int(kind); pb = proof.encode() if isinstance(proof, str) else proof; keep.append(pb); arr[i].proof = pb; arr[i].value_s = int(value_s or 0)
             for j, a in enumerate(args): hb = self.hx(a); keep.append(hb); arr[i].args[j] = hb
         ok = (ctypes.c_ubyte * max(1, len(items)))(); self.L.verifyBatch.restype = ctypes.c_int; rc = self.L.verifyBatch(arr, len(items), ok); return rc, [bool(ok[i]) for i in range(len(items))]
+    def VerifyBlock(self, items):
+        """include/zk_block.h: the same items and verdicts as VerifyBatch, by one randomized check over the block -> (accepted, [bool])"""
+        class Item(ctypes.Structure): _fields_ = [("kind", ctypes.c_int), ("proof", ctypes.c_char_p), ("args", ctypes.c_char_p * 6), ("value_s", ctypes.c_uint64)]
+        arr = (Item * max(1, len(items)))(); keep = []
+        for i, (kind, proof, args, value_s) in enumerate(items):
+            arr[i].kind = KIND[kind] if isinstance(kind, str) else int(kind); pb = proof.encode() if isinstance(proof, str) else proof; keep.append(pb); arr[i].proof = pb; arr[i].value_s = int(value_s or 0)
+            for j, a in enumerate(args): hb = self.hx(a); keep.append(hb); arr[i].args[j] = hb
+        ok = (ctypes.c_ubyte * max(1, len(items)))(); self.L.verifyBlock.restype = ctypes.c_int; rc = self.L.verifyBlock(arr, len(items), ok); return rc, [bool(ok[i]) for i in range(len(items))]
     def GenRedeemProof(self, value, value_old, sn_old, r_old, sn, r, cmtA_old, cmtA, value_s, sk):
         return self.L.genRedeemproof(ctypes.c_uint64(value), ctypes.c_uint64(value_old), self.hx(sn_old), self.hx(r_old), self.hx(sn), self.hx(r), self.hx(cmtA_old), self.hx(cmtA), ctypes.c_uint64(value_s), self.hx(sk)).decode()
     def VerifyRedeemProof(self, proof, cmtA_old, sn_old, cmtA, value_s): return bool(self.L.verifyRedeemproof(proof.encode(), self.hx(cmtA_old), self.hx(sn_old), self.hx(cmtA), ctypes.c_uint64(value_s)))

@@ -166,6 +166,20 @@ int zkgpu_verify_path_counters(const char *vk_path, uint64_t out[4]);
  * out[0] = the first round whose values differ or -1, out[1] = the slot, out[2] = the kernel's verdict (1 accept, 0 reject, 2 handed back to the host verifier) */
 int zkgpu_test_verify_trace(const char *vk_path, const char *proof_hex, const uint8_t *inputs, size_t n_inputs, uint32_t every, long out[3]);
 int zkgpu_verify_batch(const char *vk_path, const char *proofs_hex, const uint8_t *inputs, size_t n_inputs, size_t n, uint8_t *ok);
+/* The same verdicts as zkgpu_verify_batch, by ONE randomized pairing-product check over all records of the call (DESIGN.md "Block verification"):
+ *   FE(prod_i Miller(A_i, B_i)^{r_i} * Miller(-S_acc, gamma) * Miller(-S_C, delta)) == alpha_g1_beta_g2^{sum r_i}
+ * over the records that pass verifyBatch's screen; if it fails (or cannot be formed) every record is decided by the per-proof path.  Probabilistic: a call with a
+ * bad record passes the equation with probability at most 1/(2^128 - 1) over the weights.  weights: n x 16 bytes (little-endian r_i, none 0), or NULL for fresh ones from
+ * getrandom(2), a draw of 0 drawn again; by_equation (optional): 1 if the equation decided the call.  Calls of fewer than 8,192 records take the per-proof path at once. */
+int zkgpu_verify_batch_rlc(const char *vk_path, const char *proofs_hex, const uint8_t *inputs, size_t n_inputs, size_t n, const uint8_t *weights, uint8_t *ok,
+                           uint32_t *by_equation);
+/* test entries: the equation's left-hand side FE(...) for given weights (gt: 384 bytes, twelve canonical 32-byte little-endian coordinates in libff's order) and
+ * 1 if it equals the right-hand side, 0 if not — on the host with pairing_host (no device needed), or through the device path whatever the record count. */
+int zkgpu_test_verify_rlc_host(const char *vk_path, const char *proofs_hex, const uint8_t *inputs, size_t n_inputs, size_t n, const uint8_t *weights, uint8_t *gt);
+int zkgpu_test_verify_rlc_device(const char *vk_path, const char *proofs_hex, const uint8_t *inputs, size_t n_inputs, size_t n, const uint8_t *weights, uint8_t *gt);
+/* process-wide: out[0] = block equations that held, out[1] = equations that failed, out[2] = calls (zkgpu_verify_batch_rlc, verifyBlock) in which no record was
+ * decided by an equation */
+int zkgpu_verify_rlc_counters(uint64_t out[3]);
 
 #ifdef __cplusplus
 }
