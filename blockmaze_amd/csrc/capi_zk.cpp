@@ -28,6 +28,7 @@
 #include "../../include/zk_send.h"
 #include "../../include/zk_batch.h"
 #include "../../include/zk_block.h"
+#include "../../include/zk_tree.h"
 #include "../../include/zkgpu.h"
 #include "blockmaze_circuits.hpp"
 #include "groth16.hpp"
@@ -40,7 +41,9 @@ namespace {
 char *dup_string(const std::string &s) { char *p = (char *)malloc(s.size() + 1); if (p) memcpy(p, s.c_str(), s.size() + 1); return p; }
 char *hash_out(const Blob256 &h) { return dup_string(blob_to_hex(h.b, 32)); }
 std::string key_dir() { const char *e = getenv("ZK_PRFKEY_DIR"); return e && *e ? e : "/usr/local/prfKey"; }
-std::string key_path(CircuitKind k, bool pk) { return key_dir() + "/" + circuit_name(k) + (pk ? "pk.txt" : "vk.txt"); }
+// (the deposit circuit at a Merkle depth other than the reference's 8 has keys of its own: deposit<depth>pk.txt / deposit<depth>vk.txt)
+std::string key_path(CircuitKind k, bool pk, size_t depth = 8) {
+  return key_dir() + "/" + circuit_name(k) + (k == CircuitKind::Deposit && depth != 8 ? std::to_string(depth) : "") + (pk ? "pk.txt" : "vk.txt"); }
 
 struct FileStamp { off_t size = -1; time_t mtime = 0; long mtime_ns = 0; bool operator==(const FileStamp &o) const {
     return size == o.size && mtime == o.mtime && mtime_ns == o.mtime_ns; } };
@@ -71,12 +74,12 @@ struct VkSlot { FileStamp stamp; std::shared_ptr<PreparedVerifyingKey> vk; std::
   std::shared_ptr<BlockVerifier> block; int rlc_ok = -1 /* the key's check for the block equation (rlc_key_ok): -1 not made yet */; };
 std::mutex g_cache_mutex; std::map<std::string, ProverSlot> g_provers; std::map<std::string, VkSlot> g_vks;
 
-std::unique_ptr<Circuit> make_circuit(CircuitKind k, bool emit) {
+std::unique_ptr<Circuit> make_circuit(CircuitKind k, bool emit, size_t depth = 8) {
   switch (k) {
     case CircuitKind::Mint: return make_mint_circuit(emit);
     case CircuitKind::Send: return make_send_circuit(emit);
     case CircuitKind::Redeem: return make_redeem_circuit(emit);
-    default: return make_deposit_circuit(emit, 8);
+    default: return make_deposit_circuit(emit, depth);
   }
 }
 
@@ -115,8 +118,8 @@ std::condition_variable g_pool_cv;   // signalled under g_cache_mutex whenever a
 // Loads the key on first use or when the file changed. g_cache_mutex guards the slot table only; a pool is BUILT outside it (under g_gpu_mutex, which
 // serialises key loads and the other set-up work of the device), so callers that can be served by a loaded device never queue behind a key load. A prover's
 // helper threads start with its first proof (groth16_prover.cpp).
-HeldUnit acquire_prover(CircuitKind k) {
-  std::string path = key_path(k, true); FileStamp st; if (!stamp_of(path, st)) throw std::runtime_error("proving key not found: " + path);
+HeldUnit acquire_prover(CircuitKind k, size_t depth = 8) {
+  std::string path = key_path(k, true, depth); FileStamp st; if (!stamp_of(path, st)) throw std::runtime_error("proving key not found: " + path);
   const int D = std::max(1, gpu_device_slots());
   static const int spill = [] { const char *e = getenv("ZK_SPILL_BUSY"); int v = e ? atoi(e) : 1; return v < 1 ? 1 : v; }();
   std::shared_ptr<const UnitList> list; unsigned turn = 0;
@@ -160,7 +163,7 @@ HeldUnit acquire_prover(CircuitKind k) {
             u->prover.reset(new Prover(pk, 0, 1, dev));
             first = u->prover;
           } else u->prover.reset(new Prover(*first));
-          u->circuit = make_circuit(k, false); u->map_board();
+          u->circuit = make_circuit(k, false, depth); u->map_board();
           if (u->circuit->board.num_variables() != u->prover->num_variables() ||
               u->circuit->num_inputs() != u->prover->num_inputs()) throw std::runtime_error("proving key does not belong to the " +
               std::string(circuit_name(k)) + " circuit: " + path);
@@ -224,13 +227,13 @@ inline bool parse_fixed_rs(Fe32 &, Fe32 &) { return false; }
 struct ShardSet { FileStamp stamp; std::vector<std::unique_ptr<Prover>> shards; std::unique_ptr<Circuit> circuit; std::mutex busy; };
 std::mutex g_shard_mutex; std::map<std::string, std::shared_ptr<ShardSet>> g_shard_sets;
 static size_t shard_count() { static const size_t k = [] { const char *e = getenv("ZK_SHARD_DEVICES"); long v = e ? atol(e) : 0; return (size_t)(v < 2 ? 0 : v > 64 ? 64 : v); }(); return k; }
-static std::shared_ptr<ShardSet> shard_set_for(CircuitKind k) {
-  const std::string path = key_path(k, true); FileStamp st; if (!stamp_of(path, st)) throw std::runtime_error("proving key not found: " + path);
+static std::shared_ptr<ShardSet> shard_set_for(CircuitKind k, size_t depth = 8) {
+  const std::string path = key_path(k, true, depth); FileStamp st; if (!stamp_of(path, st)) throw std::runtime_error("proving key not found: " + path);
   std::lock_guard<std::mutex> lk(g_shard_mutex); std::shared_ptr<ShardSet> &slot = g_shard_sets[path];
   if (!slot || !(slot->stamp == st)) {
     std::lock_guard<std::mutex> gl(g_gpu_mutex);
     bool cached = false; ProvingKeyHost pk = load_proving_key_fast(path, cached); const size_t K = shard_count(), D = (size_t)std::max(1, gpu_device_slots());
-    auto fresh = std::make_shared<ShardSet>(); fresh->stamp = st; fresh->circuit = make_circuit(k, false);
+    auto fresh = std::make_shared<ShardSet>(); fresh->stamp = st; fresh->circuit = make_circuit(k, false, depth);
     for (size_t j = 0; j < K; j++) fresh->shards.emplace_back(new Prover(pk, j, K, (int)(j % D)));
     if (fresh->circuit->board.num_variables() != fresh->shards[0]->num_variables() || fresh->circuit->num_inputs() != fresh->shards[0]->num_inputs())
       throw std::runtime_error("proving key does not belong to the " + std::string(circuit_name(k)) + " circuit: " + path);
@@ -258,7 +261,7 @@ static bool prove_sharded(ShardSet &set, const Fe32 *r, const Fe32 *s, Proof &pr
 
 static std::atomic<int> g_proofs_in_flight{0};   // genXproof calls of this process that are between acquiring a prover and returning
 // shared tail of the gen*proof functions: assign() has filled the circuit's board
-template <class AssignFn> char *generate(CircuitKind k, AssignFn assign) {
+template <class AssignFn> char *generate(CircuitKind k, AssignFn assign, size_t depth = 8) {
   try {
     if (!gpu_available()) {
       zkgpu_set_error("no HIP device visible; libzkgpu has no CPU fallback");
@@ -272,13 +275,13 @@ template <class AssignFn> char *generate(CircuitKind k, AssignFn assign) {
     struct InFlight { InFlight() { g_proofs_in_flight.fetch_add(1, std::memory_order_relaxed); } ~InFlight() {
         g_proofs_in_flight.fetch_sub(1, std::memory_order_relaxed); } } in_flight;
     if (shard_count()) {
-      std::shared_ptr<ShardSet> set = shard_set_for(k); std::lock_guard<std::mutex> one(set->busy); assign(*set->circuit);
+      std::shared_ptr<ShardSet> set = shard_set_for(k, depth); std::lock_guard<std::mutex> one(set->busy); assign(*set->circuit);
       printf("Trying to generate %s proof...\n", circuit_name(k)); fflush(stdout);
       Fe32 r, s; const bool fixed = parse_fixed_rs(r, s); Proof proof;
       if (!prove_sharded(*set, fixed ? &r : nullptr, fixed ? &s : nullptr, proof)) { printf("can not generate %s proof\n", circuit_name(k)); fflush(stdout); proof = default_proof(); }
       return dup_string(proof_to_hex(proof));
     }
-    double t0 = now(); HeldUnit held = acquire_prover(k); ProverUnit &slot = *held.unit; double t1 = now(); assign(*slot.circuit); double t2 = now();
+    double t0 = now(); HeldUnit held = acquire_prover(k, depth); ProverUnit &slot = *held.unit; double t1 = now(); assign(*slot.circuit); double t2 = now();
     printf("Trying to generate %s proof...\n", circuit_name(k)); fflush(stdout);
     Fe32 r, s; bool fixed = parse_fixed_rs(r, s); Proof proof;
     // the board's own form (one byte per 0 / 1, Montgomery values for the rest): no conversion, no scan
@@ -310,9 +313,9 @@ template <class AssignFn> char *generate(CircuitKind k, AssignFn assign) {
 #ifndef ZK_VERIFY_WHILE_PROVING_DEFAULT
 #define ZK_VERIFY_WHILE_PROVING_DEFAULT true
 #endif
-void verify_group(CircuitKind kind, const Proof *ps, const uint8_t *parsed, const Fe32 *inputs, size_t ni, size_t m, uint8_t *res) {
+void verify_group(CircuitKind kind, const Proof *ps, const uint8_t *parsed, const Fe32 *inputs, size_t ni, size_t m, uint8_t *res, size_t depth = 8) {
   static const size_t gpu_min = [] { const char *e = getenv("ZK_VERIFY_GPU_MIN"); long v = e ? atol(e) : 1; return (size_t)(v < 1 ? 1 : v); }();
-  const std::string path = key_path(kind, false);
+  const std::string path = key_path(kind, false, depth);
   // A single proof also goes to the device while provers of this process are at work (round 6; rounds 3-5 sent it to the host verifier then: K9 took 2.1 ms idle and
   // 2.8 ms beside four provers, the host 1.87).  K9 now takes 0.74 ms and its waves run at priority 3: verifySendproof 0.85 ms on an idle GPU, 0.92 ms (median; p90 1.09)
   // beside one busy prover, 1.01 ms (p90 2.1) beside four, against 1.87-1.90 ms on a host core (profiles/r06_verify_under_load.txt).  ZK_VERIFY_WHILE_PROVING=0: the
@@ -348,14 +351,14 @@ void verify_group(CircuitKind kind, const Proof *ps, const uint8_t *parsed, cons
   }
   for (size_t j = 0; j < m; j++) res[j] = parsed[j] && res[j] == 1;
 }
-bool verify(CircuitKind k, const char *data, const std::vector<bool> &public_bits) {
+bool verify(CircuitKind k, const char *data, const std::vector<bool> &public_bits, size_t depth = 8) {
   bool ok = false;
   try {
     Proof p;
     if (data && strnlen(data, 512) == 512 && proof_from_hex(data, p)) {
       std::vector<Fe32> inputs = pack_public_bits(public_bits);
       uint8_t parsed = 1, res = 0;
-      verify_group(k, &p, &parsed, inputs.data(), inputs.size(), 1, &res);
+      verify_group(k, &p, &parsed, inputs.data(), inputs.size(), 1, &res, depth);
       ok = res == 1;
     }
   }
@@ -446,6 +449,18 @@ template <class Fn> static int guarded_prover(zkgpu_prover *h, Fn fn) {
   }
 }
 
+// the resident commitment tree's handle.  The tree locks for itself (its own mutex, then the device mutex: gpu_tree.hip), so these entries do not go through guarded().
+struct zkgpu_tree { CommitmentTree t; explicit zkgpu_tree(int depth) : t(depth) {} };
+template <class Fn> static int guarded_tree(zkgpu_tree *t, Fn fn) {
+  try {
+    if (!gpu_available()) { zkgpu_set_error("no HIP device visible; libzkgpu has no CPU fallback"); return ZKGPU_ERR_NO_DEVICE; }
+    if (!t) { zkgpu_set_error("no tree"); return ZKGPU_ERR_ARG; }
+    return fn();
+  }
+  catch (const std::exception &e) { zkgpu_set_error(e.what()); return ZKGPU_ERR_RUNTIME; }
+  catch (...) { zkgpu_set_error("unknown error"); return ZKGPU_ERR_RUNTIME; }
+}
+
 extern "C" {
 char *zkgpu_abi_genCMT(uint64_t value, char *sn_string, char *r_string) {
   return hash_out(note_cm(value, blob256_from_hex(sn_string), blob256_from_hex(r_string)));
@@ -508,8 +523,9 @@ bool zkgpu_abi_verifySendproof(char *data, char *cmtA_old, char *sn_old, char *c
 
 // depositcgo.cpp:327-444: the Merkle path of cmtS is rebuilt from cmtarray (the tree holds the leaves up to and including the first occurrence of cmtS plus
 // everything appended afterwards, i.e. all n leaves); RT is ignored and the root recomputed
-static DepositInputs deposit_inputs(uint64_t value, uint64_t value_old, char *sn_old, char *r_old, char *sn, char *r, char *sns, char *rs, char *cmtB_old,
-    char *cmtB, uint64_t value_s, char *pk, char *sn_A_old, char *cmtS, char *cmtarray, int n, char *sk, size_t depth) {
+// the statement's own fields; path, index_bits and rt come from the commitments (deposit_inputs) or from a resident tree (genDepositproofTree)
+static DepositInputs deposit_fields(uint64_t value, uint64_t value_old, char *sn_old, char *r_old, char *sn, char *r, char *sns, char *rs, char *cmtB_old,
+    char *cmtB, uint64_t value_s, char *pk, char *sn_A_old, char *cmtS, char *sk) {
   DepositInputs in;
   in.value = value;
   in.value_old = value_old;
@@ -526,6 +542,11 @@ static DepositInputs deposit_inputs(uint64_t value, uint64_t value_old, char *sn
   in.sk = blob256_from_hex(sk);
   in.pk_recv = blob160_from_hex(pk);
   in.sn_A_old = blob256_from_hex(sn_A_old);
+  return in;
+}
+static DepositInputs deposit_inputs(uint64_t value, uint64_t value_old, char *sn_old, char *r_old, char *sn, char *r, char *sns, char *rs, char *cmtB_old,
+    char *cmtB, uint64_t value_s, char *pk, char *sn_A_old, char *cmtS, char *cmtarray, int n, char *sk, size_t depth) {
+  DepositInputs in = deposit_fields(value, value_old, sn_old, r_old, sn, r, sns, rs, cmtB_old, cmtB, value_s, pk, sn_A_old, cmtS, sk);
   std::vector<Blob256> leaves = parse_cmtarray(cmtarray, n);
   size_t index = 0;
   bool found = false;
@@ -1162,6 +1183,86 @@ int verifyBlock(const zk_verify_item *items, int n, unsigned char *ok) {
   }
   catch (...) { for (int i = 0; i < n; i++) ok[i] = 0; return -1; }
 }
+
+// ---- the resident commitment tree (DESIGN.md "Commitment tree"; include/zkgpu.h, include/zk_tree.h) ---------------------------------------------------------
+zkgpu_tree *zkgpu_tree_create(int depth) {
+  zkgpu_tree *t = nullptr;
+  try {
+    if (!gpu_available()) { zkgpu_set_error("no HIP device visible; libzkgpu has no CPU fallback"); return nullptr; }
+    if (depth < 1 || depth > 32) { zkgpu_set_error("commitment tree: the depth must lie between 1 and 32"); return nullptr; }
+    t = new zkgpu_tree(depth);
+  }
+  catch (const std::exception &e) { zkgpu_set_error(e.what()); } catch (...) { zkgpu_set_error("unknown error"); }
+  return t;
+}
+void zkgpu_tree_destroy(zkgpu_tree *t) { try { delete t; } catch (...) {} }
+int zkgpu_tree_append(zkgpu_tree *t, const uint8_t *leaves, size_t n) { return guarded_tree(t, [&] {
+  if (n && !leaves) return ZKGPU_ERR_ARG;
+  if (!t->t.append(leaves, n)) { zkgpu_set_error("commitment tree: more than 2^" + std::to_string(t->t.depth()) + " leaves"); return ZKGPU_ERR_ARG; }
+  return ZKGPU_OK; }); }
+int zkgpu_tree_size(zkgpu_tree *t, uint64_t *n) { return guarded_tree(t, [&] { if (!n) return ZKGPU_ERR_ARG; *n = t->t.size(); return ZKGPU_OK; }); }
+int zkgpu_tree_root(zkgpu_tree *t, uint8_t root[32]) { return guarded_tree(t, [&] { if (!root) return ZKGPU_ERR_ARG; t->t.root(root); return ZKGPU_OK; }); }
+int zkgpu_tree_path(zkgpu_tree *t, uint64_t index, uint8_t *siblings) { return guarded_tree(t, [&] {
+  if (!siblings) return ZKGPU_ERR_ARG;
+  if (!t->t.path(index, siblings)) { zkgpu_set_error("commitment tree: no leaf " + std::to_string(index)); return ZKGPU_ERR_ARG; }
+  return ZKGPU_OK; }); }
+int zkgpu_tree_find(zkgpu_tree *t, const uint8_t leaf[32], uint64_t *index) { return guarded_tree(t, [&] {
+  if (!leaf || !index) return ZKGPU_ERR_ARG;
+  if (!t->t.find(leaf, *index)) { zkgpu_set_error("commitment tree: the leaf is not in the tree"); return ZKGPU_ERR_ARG; }
+  return ZKGPU_OK; }); }
+int zkgpu_test_tree_launches(zkgpu_tree *t, uint64_t *launches) { return guarded_tree(t, [&] { if (!launches) return ZKGPU_ERR_ARG; *launches = t->t.launches(); return ZKGPU_OK; }); }
+int zkgpu_test_tree_host(int depth, const uint8_t *leaves, size_t n, uint64_t index, uint8_t root[32], uint8_t *path) { return guarded_host([&] {
+  if (depth < 1 || depth > 32 || (n && !leaves) || n > (1ull << depth) || (path && index >= n)) return ZKGPU_ERR_ARG;
+  std::vector<Blob256> lv(n); if (n) memcpy(lv.data(), leaves, 32 * n);
+  if (root) { const Blob256 r = merkle_root(lv, (size_t)depth); memcpy(root, r.b, 32); }
+  if (path) { std::vector<bool> bits; const std::vector<Blob256> p = merkle_path(lv, (size_t)depth, (size_t)index, bits); memcpy(path, p.data(), 32 * (size_t)depth); }
+  return ZKGPU_OK; }); }
+
+zk_tree *zkTreeNew(int depth) { return zkgpu_tree_create(depth); }
+void zkTreeFree(zk_tree *t) { zkgpu_tree_destroy(t); }
+long long zkTreeAppend(zk_tree *t, char *cmtarray, int n) {
+  uint64_t size = 0;
+  const int rc = guarded_tree(t, [&] {
+    if (n < 0) return ZKGPU_ERR_ARG;
+    const size_t len = cmtarray ? strlen(cmtarray) : 0; std::vector<Blob256> leaves((size_t)n); char item[67];
+    for (size_t i = 0; i < (size_t)n; i++) {                                                     // genRoot's format (parse_cmtarray), without its limit of 256 items
+      const size_t at = i * 66, k = at < len ? std::min<size_t>(66, len - at) : 0; if (k) memcpy(item, cmtarray + at, k); item[k] = 0; leaves[i] = blob256_from_hex(item); }
+    if (!t->t.append(n ? leaves[0].b : nullptr, (size_t)n)) { zkgpu_set_error("commitment tree: more than 2^" + std::to_string(t->t.depth()) + " leaves"); return ZKGPU_ERR_ARG; }
+    size = t->t.size(); return ZKGPU_OK; });
+  if (rc != ZKGPU_OK) { fprintf(stderr, "libzkgpu: zkTreeAppend: %s\n", zkgpu_last_error()); return -1; }
+  return (long long)size;
+}
+char *zkTreeRoot(zk_tree *t) {
+  Blob256 r; if (guarded_tree(t, [&] { t->t.root(r.b); return ZKGPU_OK; }) != ZKGPU_OK) { fprintf(stderr, "libzkgpu: zkTreeRoot: %s\n", zkgpu_last_error()); return nullptr; }
+  return hash_out(r);
+}
+// genDepositproof against the resident tree: ONE snapshot gives the leaf's index, its path and the root they belong to; the proof's statement is that root
+char *genDepositproofTree(uint64_t value, uint64_t value_old, char *sn_old, char *r_old, char *sn, char *r, char *sns, char *rs, char *cmtB_old, char *cmtB,
+    uint64_t value_s, char *pk, char *sn_A_old, char *cmtS, char *sk, zk_tree *t, char rt_out[65]) {
+  if (rt_out) rt_out[0] = 0;
+  try {
+    const std::string sentinel = proof_to_hex(default_proof());
+    if (!gpu_available()) {
+      zkgpu_set_error("no HIP device visible; libzkgpu has no CPU fallback"); fprintf(stderr, "libzkgpu: no HIP device visible, cannot generate deposit proof\n");
+      return dup_string(sentinel);
+    }
+    if (!t || !rt_out) throw std::runtime_error("genDepositproofTree: no tree or no rt_out");
+    DepositInputs in = deposit_fields(value, value_old, sn_old, r_old, sn, r, sns, rs, cmtB_old, cmtB, value_s, pk, sn_A_old, cmtS, sk);
+    CommitmentTree::Snapshot snap;
+    // the reference throws out of IncrementalMerkleTree::path() here (IncrementalMerkleTree.tcc:214-216)
+    if (!t->t.snapshot(in.cmtS.b, snap)) throw std::runtime_error("cmtS is not among the commitments of the tree");
+    const size_t depth = (size_t)t->t.depth(); in.path.resize(depth); memcpy(in.path.data(), snap.path.data(), 32 * depth); in.index_bits = snap.index_bits; memcpy(in.rt.b, snap.root, 32);
+    char *proof = generate(CircuitKind::Deposit, [&](Circuit &c) { assign_deposit(c, in); }, depth);
+    if (proof && sentinel != proof) { const std::string rt = blob_to_hex(in.rt.b, 32); memcpy(rt_out, rt.c_str(), 65); }
+    return proof;
+  }
+  catch (const std::exception &e) { zkgpu_set_error(e.what()); fprintf(stderr, "libzkgpu: %s\n", e.what()); }
+  catch (...) { zkgpu_set_error("unknown error"); }
+  try { return dup_string(proof_to_hex(default_proof())); } catch (...) { return nullptr; }
+}
+bool verifyDepositproofDepth(int depth, char *data, char *RT, char *pk, char *cmtb_old, char *snold, char *cmtb, char *sns) {
+  if (depth < 1 || depth > 32) return false;
+  const char *a[6] = {RT, pk, cmtb_old, snold, cmtb, sns}; return verify(CircuitKind::Deposit, data, public_bits(CircuitKind::Deposit, a, 0), (size_t)depth); }
 
 // the reference's symbol names, exported by libzkgpu.so itself (the four libzk_*.so forward to the zkgpu_abi_* names above)
 char *genCMT(uint64_t v, char *a, char *b) { return zkgpu_abi_genCMT(v, a, b); }

@@ -144,6 +144,25 @@ class BlockVerifier {
   struct Impl; std::unique_ptr<Impl> impl;
 };
 
+// The commitment tree of the deposit circuit, resident in HBM (gpu_tree.hip): an append-only SHA-256 Merkle tree of depth 1..32 with all-zero unseen leaves,
+// the tree of notes.cpp:tree_levels.  Leaves, siblings and roots are 32-byte blobs in blob byte order.  One mutex per tree: append, root, path, find and snapshot
+// are each atomic with respect to the others, and each runs on the main stream under the device mutex.
+class CommitmentTree {
+ public:
+  // one state of the tree seen under one lock: a proof must never pair the path of one state with the root of another
+  struct Snapshot { uint64_t index = 0, size = 0; uint8_t root[32]; std::vector<uint8_t> path /* depth x 32, leaf level first */; std::vector<bool> index_bits; };
+  explicit CommitmentTree(int depth);
+  ~CommitmentTree();
+  int depth() const; uint64_t size() const;
+  bool append(const uint8_t *leaves, size_t n);                      // false: the tree would hold more than 2^depth leaves; nothing changed
+  void root(uint8_t out[32]);
+  bool path(uint64_t index, uint8_t *siblings /* depth x 32 */);      // false: no such leaf
+  bool find(const uint8_t leaf[32], uint64_t &index);                // the first leaf equal to the blob; false: none
+  bool snapshot(const uint8_t leaf[32], Snapshot &out);              // false: the leaf is not in the tree (size and root are filled all the same)
+  uint64_t launches() const;                                         // append kernels launched so far (tests: a small append is one launch)
+  struct Impl; std::unique_ptr<Impl> impl;
+};
+
 // Evaluation domain of size m = 2^k or 2^k + 2^r (libfqfft get_evaluation_domain, get_evaluation_domain.tcc:33-52) with
 // its twiddle / coset tables resident in HBM.
 struct R1csHost;

@@ -1,0 +1,219 @@
+// The commitment tree resident in HBM (DESIGN.md "Commitment tree"): an append-only SHA-256 Merkle tree of depth d, 1 <= d <= 32, as notes.cpp:tree_levels
+// restates it from IncrementalMerkleTree.tcc:179-258 — node = one compression of left || right from the standard IV, no padding; leaves are 32-byte blobs in blob
+// byte order; an unseen leaf is all zero, so a missing right sibling at level k is the empty root empty[k].
+// Layout: level k (0 = leaves ... d = root) holds c_k = ceil(n / 2^k) nodes, at least one once a leaf exists — above the first level with a single node that is the
+// spine of compress(node, empty[k]).  All levels lie in one allocation: with a leaf capacity cap0 = 2^c level k has room for max(cap0 >> k, 1) nodes and starts at
+// node offset tree_off(k).  Nodes are stored as bytes, so a path is a gather and a download.
+// Everything runs in order on the library's main stream (lane 0) under the device mutex, each entry of a tree under that tree's own mutex.
+#include <cstring>
+#include <mutex>
+#include "gpu_internal.hpp"
+
+extern std::mutex g_gpu_mutex;
+
+namespace zk {
+void sha256_compress_raw(const uint8_t left[32], const uint8_t right[32], uint8_t out[32]);   // notes.cpp (the empty roots, 32 compressions a tree)
+
+constexpr int TREE_TILE_LOG = 9, TREE_TILE = 1 << TREE_TILE_LOG;   // nodes of the base level a workgroup takes; it carries them TREE_TILE_LOG levels up
+constexpr int TREE_THREADS = 256;
+constexpr uint32_t TREE_MIN_CAP_LOG = 10;
+
+struct TreeGeom { uint8_t *nodes; const uint8_t *empty; uint32_t cap_log, depth; };
+__host__ __device__ __forceinline__ uint64_t tree_off(uint32_t cap_log, uint32_t k) {
+  const uint64_t two = 2ull << cap_log; return k <= cap_log ? two - (two >> k) : two - 2 + (k - cap_log);
+}
+__device__ __forceinline__ uint64_t tree_count(uint64_t n, uint32_t k) { return (n >> k) + ((n & ((1ull << k) - 1)) ? 1 : 0); }   // ceil(n / 2^k), k <= 32
+
+struct Node { uint32_t w[8]; };   // eight big-endian words of SHA-256, as the compression wants them
+__device__ __forceinline__ Node tree_load(const uint8_t *p) {
+  const uint4 a = ((const uint4 *)p)[0], b = ((const uint4 *)p)[1];
+  return {{__builtin_bswap32(a.x), __builtin_bswap32(a.y), __builtin_bswap32(a.z), __builtin_bswap32(a.w), __builtin_bswap32(b.x), __builtin_bswap32(b.y),
+      __builtin_bswap32(b.z), __builtin_bswap32(b.w)}};
+}
+__device__ __forceinline__ void tree_store(uint8_t *p, const Node &v) {
+  ((uint4 *)p)[0] = make_uint4(__builtin_bswap32(v.w[0]), __builtin_bswap32(v.w[1]), __builtin_bswap32(v.w[2]), __builtin_bswap32(v.w[3]));
+  ((uint4 *)p)[1] = make_uint4(__builtin_bswap32(v.w[4]), __builtin_bswap32(v.w[5]), __builtin_bswap32(v.w[6]), __builtin_bswap32(v.w[7]));
+}
+
+// (constexpr: under full unrolling every round constant is a literal of its instruction, no load and no register)
+constexpr uint32_t TREE_K256[64] = {
+    0x428a2f98, 0x71374491, 0xb5c0fbcf, 0xe9b5dba5, 0x3956c25b, 0x59f111f1, 0x923f82a4, 0xab1c5ed5, 0xd807aa98, 0x12835b01, 0x243185be, 0x550c7dc3, 0x72be5d74,
+    0x80deb1fe, 0x9bdc06a7, 0xc19bf174, 0xe49b69c1, 0xefbe4786, 0x0fc19dc6, 0x240ca1cc, 0x2de92c6f, 0x4a7484aa, 0x5cb0a9dc, 0x76f988da, 0x983e5152, 0xa831c66d,
+    0xb00327c8, 0xbf597fc7, 0xc6e00bf3, 0xd5a79147, 0x06ca6351, 0x14292967, 0x27b70a85, 0x2e1b2138, 0x4d2c6dfc, 0x53380d13, 0x650a7354, 0x766a0abb, 0x81c2c92e,
+    0x92722c85, 0xa2bfe8a1, 0xa81a664b, 0xc24b8b70, 0xc76c51a3, 0xd192e819, 0xd6990624, 0xf40e3585, 0x106aa070, 0x19a4c116, 0x1e376c08, 0x2748774c, 0x34b0bcb5,
+    0x391c0cb3, 0x4ed8aa4a, 0x5b9cca4f, 0x682e6ff3, 0x748f82ee, 0x78a5636f, 0x84c87814, 0x8cc70208, 0x90befffa, 0xa4506ceb, 0xbef9a3f7, 0xc67178f2};
+__device__ __forceinline__ uint32_t tree_rotr(uint32_t x, int n) { return __builtin_rotateright32(x, n); }
+// One compression of l || r from the standard IV (FIPS 180-4 6.2.2), one lane per node.  The message schedule is a rolling window of sixteen words in registers:
+// the loop is fully unrolled, so every index is a constant and the round constants are literals.
+__device__ __forceinline__ Node tree_compress(const Node &l, const Node &r) {
+  uint32_t w[16];
+#pragma unroll
+  for (int i = 0; i < 8; i++) { w[i] = l.w[i]; w[8 + i] = r.w[i]; }
+  const uint32_t H0 = 0x6a09e667, H1 = 0xbb67ae85, H2 = 0x3c6ef372, H3 = 0xa54ff53a, H4 = 0x510e527f, H5 = 0x9b05688c, H6 = 0x1f83d9ab, H7 = 0x5be0cd19;
+  uint32_t a = H0, b = H1, c = H2, d = H3, e = H4, f = H5, g = H6, h = H7;
+#pragma unroll
+  for (int i = 0; i < 64; i++) {
+    if (i >= 16) {
+      const uint32_t w15 = w[(i + 1) & 15], w2 = w[(i + 14) & 15];
+      w[i & 15] += (tree_rotr(w15, 7) ^ tree_rotr(w15, 18) ^ (w15 >> 3)) + w[(i + 9) & 15] + (tree_rotr(w2, 17) ^ tree_rotr(w2, 19) ^ (w2 >> 10));
+    }
+    const uint32_t t1 = h + (tree_rotr(e, 6) ^ tree_rotr(e, 11) ^ tree_rotr(e, 25)) + (g ^ (e & (f ^ g))) + TREE_K256[i] + w[i & 15];
+    const uint32_t t2 = (tree_rotr(a, 2) ^ tree_rotr(a, 13) ^ tree_rotr(a, 22)) + ((a & b) | (c & (a | b)));
+    h = g; g = f; f = e; e = d + t1; d = c; c = b; b = a; a = t1 + t2;
+  }
+  return {{a + H0, b + H1, c + H2, d + H3, e + H4, f + H5, g + H6, h + H7}};
+}
+
+// The append kernel.  The tree grew from n_old to n_new leaves and levels 0 .. k0 are up to date; level k's dirty range is lo_k = floor(n_old / 2^k) ..
+// c_k - 1 = ceil(n_new / 2^k) - 1, and nothing else of a level is computed.  A workgroup owns a window of level k0 and carries it `levels` levels up, the nodes of
+// the level just made lying in LDS (as words) for the next one, one barrier a level:
+//   tiled  (ragged = 0): the window is the aligned tile blockIdx.x + tile0 of TREE_TILE nodes, levels = TREE_TILE_LOG, so the tile ends in one node;
+//   ragged (ragged = 1): one workgroup, the window is the whole dirty range of level k0 (at most TREE_TILE nodes), levels = depth - k0: once a level's dirty range
+//                        is down to one node — the spine, or the single parent chain of a small append — lane 0 of the first wave walks it to the root alone, without barriers.
+// Outside its LDS window a node's left child is clean (older than this append: read from the level's array) and its right child does not exist (empty[k]).
+__global__ void __launch_bounds__(TREE_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8))) k_tree_append(TreeGeom G, uint64_t n_old, uint64_t n_new, uint32_t k0, uint32_t levels, uint64_t tile0, int ragged) {
+  __shared__ uint4 lds_a[(TREE_TILE / 2 + 1) * 2], lds_b[(TREE_TILE / 4 + 2) * 2];
+  const uint32_t tid = threadIdx.x;
+  const uint64_t t_lo = ragged ? 0 : (tile0 + blockIdx.x) << TREE_TILE_LOG;                      // window at level k0 (ragged: bounded by the dirty range alone)
+  // p_lo, p_cnt: this workgroup's nodes of the level below the one being made (all uniform: scalar registers)
+  uint64_t p_lo = n_old >> k0; if (t_lo > p_lo) p_lo = t_lo;
+  uint64_t p_hi = tree_count(n_new, k0); if (!ragged && t_lo + TREE_TILE < p_hi) p_hi = t_lo + TREE_TILE;
+  uint32_t p_cnt = (uint32_t)(p_hi - p_lo); bool chain = false;
+#pragma unroll 1
+  for (uint32_t j = 1; j <= levels; j++) {
+    const uint32_t k = k0 + j;
+    uint64_t lo = n_old >> k; if ((t_lo >> j) > lo) lo = t_lo >> j;
+    uint64_t hi = tree_count(n_new, k); if (!ragged && ((t_lo + TREE_TILE) >> j) < hi) hi = (t_lo + TREE_TILE) >> j;
+    const uint32_t cnt = (uint32_t)(hi - lo); const int dl = (int)(2 * lo - p_lo);                 // 0, or -1: the first node's left child is clean
+    if (ragged && p_cnt == 1 && !chain) { chain = true; if (tid) return; }                         // one dirty node below: lane 0 walks the rest, no barrier needed
+    const uint8_t *below = G.nodes + 32 * (tree_off(G.cap_log, k - 1) + p_lo), *none = G.empty + 32 * (k - 1);
+    uint8_t *here = G.nodes + 32 * (tree_off(G.cap_log, k) + lo);
+    const uint4 *src = (j & 1) ? lds_b : lds_a; uint4 *dst = (j & 1) ? lds_a : lds_b;             // level k0 + 1 goes to lds_a (up to TREE_TILE / 2 + 1 nodes)
+    for (uint32_t t = tid; t < cnt; t += TREE_THREADS) {
+      const int c = 2 * (int)t + dl; Node l, r;
+      if (j > 1 && c >= 0) { const uint4 x = src[2 * c], y = src[2 * c + 1]; l = {{x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w}}; }
+      else l = tree_load(below + 32 * c);
+      if ((uint32_t)(c + 1) >= p_cnt) r = tree_load(none);
+      else if (j > 1) { const uint4 x = src[2 * c + 2], y = src[2 * c + 3]; r = {{x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w}}; }
+      else r = tree_load(below + 32 * (c + 1));
+      const Node v = tree_compress(l, r);
+      tree_store(here + 32 * t, v);
+      dst[2 * t] = make_uint4(v.w[0], v.w[1], v.w[2], v.w[3]); dst[2 * t + 1] = make_uint4(v.w[4], v.w[5], v.w[6], v.w[7]);
+    }
+    if (!chain) __syncthreads();
+    p_lo = lo; p_cnt = cnt;
+  }
+}
+
+// first index whose leaf equals the blob, 2^64 - 1 if none of the n leaves does
+__global__ void __launch_bounds__(256) k_tree_find(const uint4 *__restrict__ leaves, uint64_t n, uint4 t0, uint4 t1, unsigned long long *__restrict__ first) {
+  unsigned long long best = ~0ull;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+    const uint4 a = leaves[2 * i], b = leaves[2 * i + 1];
+    if (a.x == t0.x && a.y == t0.y && a.z == t0.z && a.w == t0.w && b.x == t1.x && b.y == t1.y && b.z == t1.z && b.w == t1.w) { best = i; break; }   // (a lane's indices ascend)
+  }
+  if (best != ~0ull) atomicMin(first, best);
+}
+// out = [index: 8 bytes, padded to 32 | depth siblings of that leaf, leaf level first | root]; the index comes from the host or (index_dev) from k_tree_find's
+// word.  An index that is no leaf (the blob was not found) leaves the siblings unwritten.
+__global__ void __launch_bounds__(64) k_tree_path(TreeGeom G, uint64_t n, uint64_t index, const unsigned long long *__restrict__ index_dev, uint8_t *__restrict__ out) {
+  const uint32_t k = threadIdx.x; if (index_dev) index = *index_dev;
+  if (k == 0) { ((unsigned long long *)out)[0] = index; }
+  if (k == G.depth) { const uint8_t *src = n ? G.nodes + 32 * tree_off(G.cap_log, G.depth) : G.empty + 32 * G.depth; ((uint4 *)(out + 32 * (G.depth + 1)))[0] = ((const uint4 *)src)[0]; ((uint4 *)(out + 32 * (G.depth + 1)))[1] = ((const uint4 *)src)[1]; }
+  if (k >= G.depth || index >= n) return;
+  const uint64_t sib = (index >> k) ^ 1; const uint8_t *src = sib < tree_count(n, k) ? G.nodes + 32 * (tree_off(G.cap_log, k) + sib) : G.empty + 32 * k;
+  ((uint4 *)(out + 32 * (k + 1)))[0] = ((const uint4 *)src)[0]; ((uint4 *)(out + 32 * (k + 1)))[1] = ((const uint4 *)src)[1];
+}
+
+struct CommitmentTree::Impl {
+  std::mutex mu; uint32_t depth = 0, cap_log = 0; uint64_t n = 0; DevBuf<uint8_t> nodes, empty, out, first /* k_tree_find's word */; std::vector<uint8_t> empty_host;
+  uint64_t launches = 0;
+  TreeGeom geom() const { return TreeGeom{nodes.get(), empty.get(), cap_log, depth}; }
+  static size_t bytes_for(uint32_t cap_log, uint32_t depth) { return 32 * (size_t)(tree_off(cap_log, depth) + 1); }
+  // room for n_new leaves: a new allocation of twice the capacity or more, every level copied over by the library's copy kernel
+  void reserve(uint64_t n_new) {
+    if (n_new <= (1ull << cap_log)) return;
+    uint32_t c = cap_log + 1; while ((1ull << c) < n_new) c++;
+    DevBuf<uint8_t> fresh(bytes_for(c, depth));
+    for (uint32_t k = 0; k <= depth && n; k++) { const uint64_t cnt = (n >> k) + ((n & ((1ull << k) - 1)) ? 1 : 0);
+      copy_dev_async(fresh.get() + 32 * tree_off(c, k), nodes.get() + 32 * tree_off(cap_log, k), 32 * (size_t)cnt); }
+    HIP_CHECK(hipGetLastError()); HIP_CHECK(hipStreamSynchronize(gpu().stream));                  // (the old allocation is let go below)
+    nodes = std::move(fresh); cap_log = c;
+  }
+  // [index | path | root] of the current state in one download; index_dev: take the index from k_tree_find's word
+  void fetch(uint64_t index, bool index_from_find, std::vector<uint8_t> &host) {
+    hipLaunchKernelGGL(k_tree_path, dim3(1), dim3(64), 0, gpu().stream, geom(), n, index, index_from_find ? (const unsigned long long *)first.get() : nullptr, out.get());
+    HIP_CHECK(hipGetLastError()); host.resize(32 * (depth + 2)); out.download(host.data(), host.size());
+  }
+  void find_async(const uint8_t leaf[32]) {
+    HIP_CHECK(hipMemsetAsync(first.get(), 0xff, 8, gpu().stream)); if (!n) return;
+    uint4 t[2]; memcpy(t, leaf, 32); const unsigned nb = (unsigned)std::min<uint64_t>(cdiv(n, 256), 2048);
+    hipLaunchKernelGGL(k_tree_find, dim3(nb), dim3(256), 0, gpu().stream, (const uint4 *)nodes.get(), n, t[0], t[1], (unsigned long long *)first.get());
+  }
+};
+
+CommitmentTree::CommitmentTree(int depth) : impl(new Impl) {
+  if (depth < 1 || depth > 32) throw GpuError("commitment tree: the depth must lie between 1 and 32");
+  LaneScope lane(0); std::lock_guard<std::mutex> gl(g_gpu_mutex); Impl &d = *impl; d.depth = (uint32_t)depth; d.cap_log = std::min<uint32_t>(TREE_MIN_CAP_LOG, d.depth);
+  d.empty_host.assign(32 * (depth + 1), 0);
+  for (int k = 1; k <= depth; k++) sha256_compress_raw(&d.empty_host[32 * (k - 1)], &d.empty_host[32 * (k - 1)], &d.empty_host[32 * k]);
+  d.nodes = DevBuf<uint8_t>(Impl::bytes_for(d.cap_log, d.depth)); d.empty = DevBuf<uint8_t>(d.empty_host.size()); d.out = DevBuf<uint8_t>(32 * (depth + 2));
+  d.first = DevBuf<uint8_t>(8); d.empty.upload(d.empty_host.data(), d.empty_host.size());
+}
+CommitmentTree::~CommitmentTree() { try { LaneScope lane(0); std::lock_guard<std::mutex> gl(g_gpu_mutex); impl.reset(); } catch (...) {} }
+int CommitmentTree::depth() const { return (int)impl->depth; }
+uint64_t CommitmentTree::size() const { std::lock_guard<std::mutex> lk(impl->mu); return impl->n; }
+uint64_t CommitmentTree::launches() const { std::lock_guard<std::mutex> lk(impl->mu); return impl->launches; }
+
+bool CommitmentTree::append(const uint8_t *leaves, size_t count) {
+  Impl &d = *impl; std::lock_guard<std::mutex> lk(d.mu);
+  if (count > (1ull << d.depth) - d.n) return false;
+  if (!count) return true;
+  LaneScope lane(0); std::lock_guard<std::mutex> gl(g_gpu_mutex); hipStream_t s = gpu().stream;
+  const uint64_t n_old = d.n, n_new = d.n + count; d.reserve(n_new);
+  { Stage up("tree.upload"); HIP_CHECK(hipMemcpyAsync(d.nodes.get() + 32 * n_old, leaves, 32 * count, hipMemcpyHostToDevice, s)); }
+  // tiled launches while the dirty range of the base level is wider than one window, then the ragged one to the root
+  { Stage st("tree.append");                                                                     // (HIP events when profiling is on: tools/tree_bench.py)
+  for (uint32_t k0 = 0;;) {
+    const uint64_t lo = n_old >> k0, hi = (n_new >> k0) + ((n_new & ((1ull << k0) - 1)) ? 1 : 0);
+    if (hi - lo <= TREE_TILE || k0 + TREE_TILE_LOG >= d.depth) {
+      // (a base level that is too wide can only be left here if depth - k0 <= TREE_TILE_LOG, and then 2^depth >> k0 <= TREE_TILE bounds it: never)
+      hipLaunchKernelGGL(k_tree_append, dim3(1), dim3(TREE_THREADS), 0, s, d.geom(), n_old, n_new, k0, d.depth - k0, (uint64_t)0, 1); d.launches++;
+      break;
+    }
+    const uint64_t t0 = lo >> TREE_TILE_LOG, t1 = (hi - 1) >> TREE_TILE_LOG;
+    hipLaunchKernelGGL(k_tree_append, dim3((unsigned)(t1 - t0 + 1)), dim3(TREE_THREADS), 0, s, d.geom(), n_old, n_new, k0, (uint32_t)TREE_TILE_LOG, t0, 0); d.launches++;
+    k0 += TREE_TILE_LOG;
+  } }
+  HIP_CHECK(hipGetLastError()); HIP_CHECK(hipStreamSynchronize(s));
+  d.n = n_new; return true;
+}
+void CommitmentTree::root(uint8_t out[32]) {
+  Impl &d = *impl; std::lock_guard<std::mutex> lk(d.mu);
+  if (!d.n) { memcpy(out, &d.empty_host[32 * d.depth], 32); return; }
+  LaneScope lane(0); std::lock_guard<std::mutex> gl(g_gpu_mutex); hipStream_t s = gpu().stream;
+  HIP_CHECK(hipMemcpyAsync(out, d.nodes.get() + 32 * tree_off(d.cap_log, d.depth), 32, hipMemcpyDeviceToHost, s)); HIP_CHECK(hipStreamSynchronize(s));
+}
+bool CommitmentTree::path(uint64_t index, uint8_t *siblings) {
+  Impl &d = *impl; std::lock_guard<std::mutex> lk(d.mu); if (index >= d.n) return false;
+  LaneScope lane(0); std::lock_guard<std::mutex> gl(g_gpu_mutex); std::vector<uint8_t> h; d.fetch(index, false, h);
+  memcpy(siblings, h.data() + 32, 32 * d.depth); return true;
+}
+bool CommitmentTree::find(const uint8_t leaf[32], uint64_t &index) {
+  Impl &d = *impl; std::lock_guard<std::mutex> lk(d.mu); if (!d.n) return false;
+  LaneScope lane(0); std::lock_guard<std::mutex> gl(g_gpu_mutex); d.find_async(leaf); HIP_CHECK(hipGetLastError());
+  uint64_t got = 0; d.first.download((uint8_t *)&got, 8); if (got >= d.n) return false;
+  index = got; return true;
+}
+bool CommitmentTree::snapshot(const uint8_t leaf[32], Snapshot &out) {
+  Impl &d = *impl; std::lock_guard<std::mutex> lk(d.mu); out.size = d.n; out.path.assign(32 * d.depth, 0); out.index_bits.assign(d.depth, false); out.index = 0;
+  if (!d.n) { memcpy(out.root, &d.empty_host[32 * d.depth], 32); return false; }
+  LaneScope lane(0); std::lock_guard<std::mutex> gl(g_gpu_mutex); std::vector<uint8_t> h; d.find_async(leaf); d.fetch(0, true, h);   // find, gather, one download
+  memcpy(out.root, h.data() + 32 * (d.depth + 1), 32);
+  uint64_t got; memcpy(&got, h.data(), 8); if (got >= d.n) return false;
+  out.index = got; memcpy(out.path.data(), h.data() + 32, 32 * d.depth);
+  for (uint32_t k = 0; k < d.depth; k++) out.index_bits[k] = (got >> k) & 1;
+  return true;
+}
+
+}  // namespace zk

@@ -251,12 +251,48 @@ def verify(vk_path, proof_hex, inputs):
     if rc < 0: _check(rc)
     return bool(rc)
 
+# ---- the commitment tree resident in HBM (include/zkgpu.h "commitment tree") ---------------------------------------------
+class Tree:
+    """append-only SHA-256 Merkle tree of depth 1..32 on the device; leaves, siblings and roots are 32-byte strings in blob order (the reverse of the hex the cgo symbols print)"""
+    def __init__(self, depth):
+        lib().zkgpu_tree_create.restype = ctypes.c_void_p; self.depth = int(depth); self.h = lib().zkgpu_tree_create(self.depth)
+        if not self.h: raise ZkGpuError(lib().zkgpu_last_error().decode())
+    def append(self, leaves):
+        """leaves: a list of 32-byte strings, or one bytes object of n x 32 bytes"""
+        buf = leaves if isinstance(leaves, (bytes, bytearray)) else b"".join(bytes(x) for x in leaves); assert len(buf) % 32 == 0
+        _check(lib().zkgpu_tree_append(ctypes.c_void_p(self.h), bytes(buf), ctypes.c_size_t(len(buf) // 32)))
+    def size(self):
+        n = ctypes.c_uint64(0); _check(lib().zkgpu_tree_size(ctypes.c_void_p(self.h), ctypes.byref(n))); return int(n.value)
+    def root(self):
+        out = ctypes.create_string_buffer(32); _check(lib().zkgpu_tree_root(ctypes.c_void_p(self.h), out)); return out.raw
+    def path(self, index):
+        """the siblings of leaf `index`, leaf level first"""
+        out = ctypes.create_string_buffer(32 * self.depth); _check(lib().zkgpu_tree_path(ctypes.c_void_p(self.h), ctypes.c_uint64(index), out)); return [out.raw[32 * k:32 * k + 32] for k in range(self.depth)]
+    def find(self, leaf):
+        """index of the first leaf equal to the blob; raises ZkGpuError if there is none"""
+        i = ctypes.c_uint64(0); _check(lib().zkgpu_tree_find(ctypes.c_void_p(self.h), bytes(leaf), ctypes.byref(i))); return int(i.value)
+    def launches(self):
+        k = ctypes.c_uint64(0); _check(lib().zkgpu_test_tree_launches(ctypes.c_void_p(self.h), ctypes.byref(k))); return int(k.value)
+    def close(self):
+        if self.h: lib().zkgpu_tree_destroy(ctypes.c_void_p(self.h)); self.h = None
+    def __del__(self):
+        try: self.close()
+        except Exception: pass
+def tree_host(depth, leaves, index=None, want_root=True):
+    """the host model of the same tree (notes.cpp: tree_levels), no device needed -> (root or None, siblings of `index` leaf level first or None)"""
+    buf = leaves if isinstance(leaves, (bytes, bytearray)) else b"".join(bytes(x) for x in leaves); n = len(buf) // 32
+    root = ctypes.create_string_buffer(32) if want_root else None; path = ctypes.create_string_buffer(32 * depth) if index is not None else None
+    _check(lib().zkgpu_test_tree_host(int(depth), bytes(buf) if n else None, ctypes.c_size_t(n), ctypes.c_uint64(index or 0), root, path))
+    return (root.raw if want_root else None), ([path.raw[32 * k:32 * k + 32] for k in range(depth)] if path is not None else None)
+
 class Zk:
     """the drop-in symbols (what go-ethereum/zktx calls through cgo), bound the way zktx.go marshals them: "0x…" hex strings and uint64"""
     def __init__(self):
         L = lib()
         for f in ("genCMT", "genCMTS", "computePRF", "computeCRH", "genRoot", "genMintproof", "genSendproof", "genRedeemproof", "genDepositproof"): getattr(L, f).restype = ctypes.c_char_p
         for f in ("verifyMintproof", "verifySendproof", "verifyRedeemproof", "verifyDepositproof"): getattr(L, f).restype = ctypes.c_bool
+        for f in ("zkTreeRoot", "genDepositproofTree"): getattr(L, f).restype = ctypes.c_char_p
+        L.zkTreeNew.restype = ctypes.c_void_p; L.zkTreeAppend.restype = ctypes.c_longlong; L.verifyDepositproofDepth.restype = ctypes.c_bool
         self.L = L
     @staticmethod
     def hx(b): return ("0x" + bytes(b).hex()).encode()          # common.ToHex
@@ -294,3 +330,21 @@ class Zk:
     def GenRedeemProof(self, value, value_old, sn_old, r_old, sn, r, cmtA_old, cmtA, value_s, sk):
         return self.L.genRedeemproof(ctypes.c_uint64(value), ctypes.c_uint64(value_old), self.hx(sn_old), self.hx(r_old), self.hx(sn), self.hx(r), self.hx(cmtA_old), self.hx(cmtA), ctypes.c_uint64(value_s), self.hx(sk)).decode()
     def VerifyRedeemProof(self, proof, cmtA_old, sn_old, cmtA, value_s): return bool(self.L.verifyRedeemproof(proof.encode(), self.hx(cmtA_old), self.hx(sn_old), self.hx(cmtA), ctypes.c_uint64(value_s)))
+    # include/zk_tree.h: the resident commitment tree at the drop-in level (hex strings as zktx.go marshals them)
+    def TreeNew(self, depth):
+        t = self.L.zkTreeNew(int(depth))
+        if not t: raise ZkGpuError(lib().zkgpu_last_error().decode())
+        return t
+    def TreeFree(self, t): self.L.zkTreeFree(ctypes.c_void_p(t))
+    def TreeAppend(self, t, cmts):
+        """-> the new number of leaves, -1 on failure"""
+        return int(self.L.zkTreeAppend(ctypes.c_void_p(t), b"".join(self.hx(c) for c in cmts), len(cmts)))
+    def TreeRoot(self, t): return bytes.fromhex(self.L.zkTreeRoot(ctypes.c_void_p(t)).decode())
+    def GenDepositProofTree(self, value, value_old, sn_old, r_old, sn, r, sns, rs, cmtB_old, cmtB, value_s, pk, sn_A_old, cmtS, sk, t):
+        """-> (proof hex, root the proof was made against as big-endian bytes, or None on failure)"""
+        rt = ctypes.create_string_buffer(65)
+        p = self.L.genDepositproofTree(ctypes.c_uint64(value), ctypes.c_uint64(value_old), self.hx(sn_old), self.hx(r_old), self.hx(sn), self.hx(r), self.hx(sns), self.hx(rs), self.hx(cmtB_old), self.hx(cmtB), ctypes.c_uint64(value_s),
+                                       self.hx(pk), self.hx(sn_A_old), self.hx(cmtS), self.hx(sk), ctypes.c_void_p(t) if t else None, rt).decode()
+        return p, (bytes.fromhex(rt.value.decode()) if rt.value else None)
+    def VerifyDepositProofDepth(self, depth, proof, RT, pk, cmtb_old, sn_old, cmtb, sns):
+        return bool(self.L.verifyDepositproofDepth(int(depth), proof.encode(), self.hx(RT), self.hx(pk), self.hx(cmtb_old), self.hx(sn_old), self.hx(cmtb), self.hx(sns)))

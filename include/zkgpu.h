@@ -181,6 +181,22 @@ int zkgpu_test_verify_rlc_device(const char *vk_path, const char *proofs_hex, co
  * decided by an equation */
 int zkgpu_verify_rlc_counters(uint64_t out[3]);
 
+/* ---- the commitment tree resident in HBM (DESIGN.md "Commitment tree"; the drop-in level is zk_tree.h) -------------------------------------------------
+ * An append-only SHA-256 Merkle tree of depth 1..32: node = one compression of left || right from the standard IV without padding, unseen leaves all zero
+ * (IncrementalMerkleTree.tcc:179-258, the tree of genRoot at depth 8).  Leaves, siblings and roots are 32 bytes in blob order: the reverse of the 64 hex digits
+ * the cgo symbols print.  Entries of one tree are atomic with respect to each other and may be called from any thread. */
+typedef struct zkgpu_tree zkgpu_tree;
+zkgpu_tree *zkgpu_tree_create(int depth);                                   /* NULL + zkgpu_last_error() on failure */
+void zkgpu_tree_destroy(zkgpu_tree *t);
+int zkgpu_tree_append(zkgpu_tree *t, const uint8_t *leaves, size_t n);      /* ZKGPU_ERR_ARG if the tree would overflow; nothing changes then */
+int zkgpu_tree_size(zkgpu_tree *t, uint64_t *n);
+int zkgpu_tree_root(zkgpu_tree *t, uint8_t root[32]);
+int zkgpu_tree_path(zkgpu_tree *t, uint64_t index, uint8_t *siblings /* depth x 32, leaf level first */);
+int zkgpu_tree_find(zkgpu_tree *t, const uint8_t leaf[32], uint64_t *index); /* the first index holding the blob; ZKGPU_ERR_ARG if absent */
+int zkgpu_test_tree_launches(zkgpu_tree *t, uint64_t *launches);            /* test entry: append kernels launched for this tree so far */
+/* test entry, host only: root (if root != NULL) and, if path != NULL, the path of `index` by notes.cpp's tree_levels */
+int zkgpu_test_tree_host(int depth, const uint8_t *leaves, size_t n, uint64_t index, uint8_t root[32], uint8_t *path);
+
 #ifdef __cplusplus
 }
 #endif
