@@ -28,6 +28,7 @@
 #include "../../include/zk_send.h"
 #include "../../include/zk_batch.h"
 #include "../../include/zk_block.h"
+#include "../../include/zk_records.h"
 #include "../../include/zk_tree.h"
 #include "../../include/zkgpu.h"
 #include "blockmaze_circuits.hpp"
@@ -1048,19 +1049,50 @@ static void fresh_weights(uint8_t *w, size_t n) {
   for (size_t i = 0; i < n; i++) while (is_zero_weight(w + 16 * i)) random_bytes(w + 16 * i, 16);
 }
 // one key's share of the equation: the device half, then S_acc on the host.  false: this key cannot take part (it fails rlc_key_ok).  in_eq: records flagged 1
-struct RlcPart { std::vector<uint8_t> flags; host::HFq12 prod; host::HG1 s_acc, s_c; uint64_t s[4]; size_t in_eq = 0; };
+// (from records: `sums` = the device's integer sums, `handed` = the records flagged 2 with their device-made proof and inputs, for verify_proof)
+struct RlcHanded { size_t i; Proof p; std::vector<Fe32> in; };
+struct RlcPart { std::vector<uint8_t> flags; host::HFq12 prod; host::HG1 s_acc, s_c; uint64_t s[4]; size_t in_eq = 0; std::vector<uint64_t> sums; std::vector<RlcHanded> handed; };
 static bool rlc_part(const std::string &path, const Proof *ps, const Fe32 *inputs, size_t ni, size_t m, const uint8_t *w, bool lock, RlcPart &out) {
   std::unique_lock<std::mutex> gl(g_gpu_mutex, std::defer_lock); if (lock) gl.lock();
   std::shared_ptr<BlockVerifier> bv = block_verifier_for_path(path); if (!bv) return false;
   if (bv->num_inputs() != ni) throw std::runtime_error("block verify: input count");
-  out.flags.assign(m, 0); bv->run(ps, inputs, w, m, out.flags.data(), out.prod, out.s_c); if (lock) gl.unlock();
+  out.flags.assign(m, 0); out.handed.clear(); bv->run(ps, inputs, w, m, out.flags.data(), out.prod, out.s_c); if (lock) gl.unlock();
+  for (size_t i = 0; i < m; i++) if (out.flags[i] == 2) out.handed.push_back(RlcHanded{i, ps[i], std::vector<Fe32>(inputs + i * ni, inputs + (i + 1) * ni)});
   out.s_acc = rlc_acc_sum(*vk_for_path(path), inputs, ni, w, out.flags.data(), m, out.s);
   out.in_eq = 0; for (size_t i = 0; i < m; i++) out.in_eq += out.flags[i] == 1;
   return true;
 }
-// verdicts of a part whose equation held: the screen's rejections, the per-proof host verifier for an accumulator at infinity
-static void decide_from_flags(const std::string &path, const RlcPart &p, const Proof *ps, const uint8_t *parsed, const Fe32 *inputs, size_t ni, size_t m, uint8_t *res) {
-  for (size_t i = 0; i < m; i++) res[i] = !parsed[i] ? 0 : p.flags[i] == 1 ? 1 : p.flags[i] == 2 ? (verify_proof(*vk_for_path(path), inputs + i * ni, ni, ps[i]) ? 1 : 0) : 0;
+// verdicts of a part whose equation held: the screen's rejections, the per-proof host verifier for an accumulator at infinity (the records in `handed`).  parsed: one
+// byte a record, or null where the `parsed` byte is part of the device's screen already (calls from records: a record flagged 1 or 2 is a parsed one)
+static void decide_from_flags(const std::string &path, const RlcPart &p, const uint8_t *parsed, size_t ni, size_t m, uint8_t *res) {
+  for (size_t i = 0; i < m; i++) res[i] = (!parsed || parsed[i]) && p.flags[i] == 1 ? 1 : 0;
+  for (const RlcHanded &h : p.handed) res[h.i] = (!parsed || parsed[h.i]) && verify_proof(*vk_for_path(path), h.in.data(), ni, h.p) ? 1 : 0;
+}
+// The engine entries' decision, shared by zkgpu_verify_batch_rlc and zkgpu_verify_records_rlc: from RLC_MIN_RECORDS records on the equation (`part` makes the call's
+// device half), otherwise or if it fails, cannot be formed or throws, `per_proof` (exactly zkgpu_verify_batch).  The caller holds the device mutex.
+extern "C++" {
+template <class Part, class PerProof> static int rlc_engine_call(const char *vk_path, const uint8_t *parsed, size_t ni, size_t n, uint8_t *ok, uint32_t *by_equation,
+    Part part, PerProof per_proof) {
+  bool decided = false;
+  if (n >= RLC_MIN_RECORDS) {
+    try {
+      RlcPart p;
+      if (part(p) && p.in_eq && !p.s_acc.is_inf() && !p.s_c.is_inf()) {
+        const bool pass = host::final_exponentiation(rlc_lhs(*vk_for_path(vk_path), p.prod, p.s_acc, p.s_c)) == rlc_rhs(*vk_for_path(vk_path), p.s);
+        (pass ? g_rlc_passed : g_rlc_failed).fetch_add(1);
+        if (pass) { decide_from_flags(vk_path, p, parsed, ni, n, ok); decided = true; }
+      }
+    } catch (const std::exception &e) { fprintf(stderr, "libzkgpu: block check failed (%s); deciding %zu proof(s) one by one\n", e.what(), n); }
+  }
+  if (!decided) { g_rlc_per_proof.fetch_add(1); per_proof(); }
+  if (by_equation) *by_equation = decided ? 1 : 0;
+  return ZKGPU_OK;
+}
+}  // extern "C++"
+// the per-proof tail of both: kernel K9, then the host verifier for its verdict 2
+static void per_proof_verdicts(const char *vk_path, BatchVerifier &v, const Proof *ps, const uint8_t *parsed, const Fe32 *in, size_t ni, size_t n, uint8_t *ok) {
+  v.verify(ps, in, n, ok);
+  for (size_t i = 0; i < n; i++) { if (!parsed[i]) ok[i] = 0; else if (ok[i] == 2) ok[i] = verify_proof(*vk_for_path(vk_path), in + i * ni, ni, ps[i]) ? 1 : 0; }
 }
 static void gt_bytes(const host::HFq12 &g, uint8_t out[384]) {
   host::HFq c[12]; static_assert(sizeof(c) == sizeof(g), "GT layout"); memcpy(c, &g, sizeof c);
@@ -1089,23 +1121,8 @@ int zkgpu_verify_batch_rlc(const char *vk_path, const char *proofs_hex, const ui
   std::shared_ptr<BatchVerifier> v = gpu_verifier_for_path(vk_path); const Fe32 *in = (const Fe32 *)inputs;
   if (v->num_inputs() != n_inputs) { for (size_t i = 0; i < n; i++) ok[i] = 0; g_rlc_per_proof.fetch_add(1); return ZKGPU_OK; }   // strong IC
   std::vector<Proof> ps; std::vector<uint8_t> parsed; parse_records(proofs_hex, n, ps, parsed);
-  bool decided = false;
-  if (n >= RLC_MIN_RECORDS) {
-    try {
-      RlcPart p;
-      if (rlc_part(vk_path, ps.data(), in, n_inputs, n, w.data(), false, p) && p.in_eq && !p.s_acc.is_inf() && !p.s_c.is_inf()) {
-        const bool pass = host::final_exponentiation(rlc_lhs(*vk_for_path(vk_path), p.prod, p.s_acc, p.s_c)) == rlc_rhs(*vk_for_path(vk_path), p.s);
-        (pass ? g_rlc_passed : g_rlc_failed).fetch_add(1);
-        if (pass) { decide_from_flags(vk_path, p, ps.data(), parsed.data(), in, n_inputs, n, ok); decided = true; }
-      }
-    } catch (const std::exception &e) { fprintf(stderr, "libzkgpu: block check failed (%s); deciding %zu proof(s) one by one\n", e.what(), n); }
-  }
-  if (!decided) {                                                                  // the per-proof path: exactly zkgpu_verify_batch
-    g_rlc_per_proof.fetch_add(1); v->verify(ps.data(), in, n, ok);
-    for (size_t i = 0; i < n; i++) { if (!parsed[i]) ok[i] = 0; else if (ok[i] == 2) ok[i] = verify_proof(*vk_for_path(vk_path), in + i * n_inputs, n_inputs, ps[i]) ? 1 : 0; }
-  }
-  if (by_equation) *by_equation = decided ? 1 : 0;
-  return ZKGPU_OK; }); }
+  return rlc_engine_call(vk_path, parsed.data(), n_inputs, n, ok, by_equation, [&](RlcPart &p) { return rlc_part(vk_path, ps.data(), in, n_inputs, n, w.data(), false, p); },
+      [&] { per_proof_verdicts(vk_path, *v, ps.data(), parsed.data(), in, n_inputs, n, ok); }); }); }
 // test entries: the left-hand side's GT value FE(...) and whether it equals the right-hand side, for given weights, on the device (whatever the record count) or on
 // the host.  Points at infinity contribute 1 (no fallback here).  Returns 1 / 0, or an error
 int zkgpu_test_verify_rlc_device(const char *vk_path, const char *proofs_hex, const uint8_t *inputs, size_t n_inputs, size_t n, const uint8_t *weights, uint8_t *gt) {
@@ -1130,25 +1147,85 @@ int zkgpu_verify_rlc_counters(uint64_t out[3]) {
   out[0] = g_rlc_passed.load(); out[1] = g_rlc_failed.load(); out[2] = g_rlc_per_proof.load(); return ZKGPU_OK;
 }
 
-// verifyBlock (include/zk_block.h): the records grouped by kind as verifyBatch groups them.  A kind with at least RLC_MIN_RECORDS records (and the right input
-// count) takes part in the block's equation: its left-hand factor goes into one Fq12 value, its alpha_beta^s into one right-hand side, and the block takes ONE
-// final exponentiation.  Every other kind — a small one, one whose key fails rlc_key_ok, one with no record in the equation or a sum at infinity — goes through
-// verify_group exactly as in verifyBatch, and so does every kind of the equation if the equation fails or a device step throws.
-int verifyBlock(const zk_verify_item *items, int n, unsigned char *ok) {
-  if (n < 0 || (n && (!items || !ok))) return -1;
+// ---- from records (include/zk_records.h; DESIGN.md "Block verification", "From records") ---------------------------------------------------------------------
+// A block as the node holds it: 720-byte records, the proof as its 512 characters and the statement as the bytes of its hashes.  On the equation's path nothing
+// derived from them is computed on the host: the records of a kind are gathered into pinned memory, uploaded once, and k_ingest_records makes the proof records, the
+// packed inputs and a `parsed` byte where BlockVerifier::run_resident reads them; the integer sums of the right-hand scalars come back from the device too.
+// records_to_host is the same conversion written from the functions verifyBatch uses — the road without a device, after a device failure, and the model the
+// kernel is tested against.
+namespace {
+static RecordIngest &record_ingest() { static RecordIngest *g = new RecordIngest(); return *g; }   // one staging area a process; the caller holds the device mutex
+static const zk_block_record &record_at(const zk_block_record *recs, const int *idx, size_t j) { return recs[idx ? (size_t)idx[j] : j]; }
+// Below this many records of a kind the host converter is used even where a device is there: a conversion costs the host 3.7 us a record, the device about
+// 0.4 ms a kind whatever the count (profiles/verify_records.txt): the device pays from about 100 records on.
+static const size_t INGEST_DEVICE_MIN = 256;
+static void records_to_host(const zk_block_record *recs, const int *idx, size_t m, CircuitKind kind, std::vector<Proof> &ps, std::vector<uint8_t> &parsed,
+    std::vector<Fe32> &inputs) {
+  const size_t ni = record_num_inputs((int)kind); ps.assign(m, Proof()); parsed.assign(m, 0); inputs.resize(m * ni);
+  for (size_t j = 0; j < m; j++) {
+    const zk_block_record &r = record_at(recs, idx, j); char hex[513]; memcpy(hex, r.proof, 512); hex[512] = 0;
+    parsed[j] = strnlen(hex, 512) == 512 && proof_from_hex(hex, ps[j]);
+    if (!parsed[j]) memset(&ps[j], 0, sizeof(Proof));
+    // the statement of public_bits(): a blob is the hash's bytes reversed (what blob256_from_hex makes of common.ToHex's string)
+    std::vector<bool> bits; auto blob = [&](int a, size_t nbytes) { uint8_t b[32]; for (size_t i = 0; i < nbytes; i++) b[i] = r.args[a][nbytes - 1 - i]; append(bits, blob_bits(b, nbytes)); };
+    switch (kind) {
+      case CircuitKind::Mint: case CircuitKind::Redeem: blob(0, 32); blob(1, 32); blob(2, 32); append(bits, u64_bits(r.value_s)); break;
+      case CircuitKind::Send: blob(0, 32); blob(1, 32); blob(2, 32); blob(3, 32); break;
+      default: blob(0, 32); blob(1, 20); blob(2, 32); blob(3, 32); blob(4, 32); blob(5, 32); break;
+    }
+    const std::vector<Fe32> in = pack_public_bits(bits); if (in.size() != ni) throw std::runtime_error("block records: input count");
+    memcpy(&inputs[j * ni], in.data(), ni * sizeof(Fe32));
+  }
+}
+static void stage_records(RecordIngest &ing, const zk_block_record *recs, const int *idx, size_t m) {
+  HostSpan span("host.staging"); uint8_t *st = ing.stage(m);
+  if (!idx) memcpy(st, recs, m * sizeof(zk_block_record));
+  else for (size_t j = 0; j < m; j++) memcpy(st + j * sizeof(zk_block_record), &recs[idx[j]], sizeof(zk_block_record));
+}
+// the same three arrays made by the device and brought back (the per-proof path takes host arrays)
+static void records_to_host_by_device(const zk_block_record *recs, const int *idx, size_t m, CircuitKind kind, std::vector<Proof> &ps, std::vector<uint8_t> &parsed,
+    std::vector<Fe32> &inputs, bool lock) {
+  const size_t ni = record_num_inputs((int)kind); ps.assign(m, Proof()); parsed.assign(m, 0); inputs.resize(m * ni);
+  std::unique_lock<std::mutex> gl(g_gpu_mutex, std::defer_lock); if (lock) gl.lock();
+  RecordIngest &ing = record_ingest(); stage_records(ing, recs, idx, m); ing.run(m, (int)kind, proof_encoding_strict()); ing.download(0, m, ps.data(), inputs.data(), parsed.data());
+}
+// rlc_part from records: ingest, the device half on the resident arrays, the integer sums from the device; the host keeps their reduction and the IC products
+static bool rlc_part_records(const std::string &path, CircuitKind kind, const zk_block_record *recs, const int *idx, size_t m, const uint8_t *w, bool lock, RlcPart &out) {
+  const size_t ni = record_num_inputs((int)kind);
+  { std::unique_lock<std::mutex> gl(g_gpu_mutex, std::defer_lock); if (lock) gl.lock();
+    std::shared_ptr<BlockVerifier> bv = block_verifier_for_path(path); if (!bv) return false;
+    if (bv->num_inputs() != ni) throw std::runtime_error("block verify: input count");
+    RecordIngest &ing = record_ingest(); stage_records(ing, recs, idx, m); ing.run(m, (int)kind, proof_encoding_strict());
+    out.flags.assign(m, 0); out.sums.assign((ni + 1) * 7, 0); out.handed.clear();
+    bv->run_resident(ing.items_dev(), ing.inputs_dev(), ing.parsed_dev(), w, m, out.flags.data(), out.prod, out.s_c, out.sums.data());
+    for (size_t i = 0; i < m; i++) if (out.flags[i] == 2) { RlcHanded h; h.i = i; h.in.resize(ni); ing.download(i, 1, &h.p, h.in.data(), nullptr); out.handed.push_back(std::move(h)); } }
+  { HostSpan span("host.s_acc"); out.s_acc = rlc_acc_from_sums(*vk_for_path(path), out.sums.data(), ni, out.s); }
+  out.in_eq = 0; for (size_t i = 0; i < m; i++) out.in_eq += out.flags[i] == 1;
+  return true;
+}
+// host arrays of a kind's records for the per-proof path: from the device where there is one and the kind is large enough to pay for the trip, else (or if that
+// fails) from the host converter
+static void records_for_per_proof(const zk_block_record *recs, const int *idx, size_t m, CircuitKind kind, std::vector<Proof> &ps, std::vector<uint8_t> &parsed,
+    std::vector<Fe32> &inputs, bool lock) {
+  if (m >= INGEST_DEVICE_MIN && gpu_available()) {
+    try { records_to_host_by_device(recs, idx, m, kind, ps, parsed, inputs, lock); return; }
+    catch (const std::exception &e) { fprintf(stderr, "libzkgpu: record ingest failed (%s); converting %zu record(s) on the host\n", e.what(), m); }
+  }
+  records_to_host(recs, idx, m, kind, ps, parsed, inputs);
+}
+// The decision of a block of records (verifyBlockRecords, and verifyBlock behind its conversion): the records grouped by kind as verifyBatch groups them.  A kind
+// with at least RLC_MIN_RECORDS records (and the right input count) takes part in the block's equation: its left-hand factor goes into one Fq12 value, its
+// alpha_beta^s into one right-hand side, and the block takes ONE final exponentiation.  Every other kind — a small one, one whose key fails rlc_key_ok, one with no
+// record in the equation or a sum at infinity — goes through verify_group exactly as in verifyBatch, and so does every kind of the equation if the equation fails or
+// a device step throws.
+static int verify_block_records(const zk_block_record *recs, int n, unsigned char *ok, const char *who) {
   try {
-    struct Group { CircuitKind kind; std::string path; std::vector<int> idx; std::vector<Proof> ps; std::vector<uint8_t> parsed, res; std::vector<Fe32> inputs; size_t ni = 0;
-      RlcPart part; bool in_eq = false, decided = false; };
+    struct Group { CircuitKind kind; std::string path; std::vector<int> idx; std::vector<uint8_t> res; size_t ni = 0; RlcPart part; bool in_eq = false, decided = false; };
     std::vector<Group> groups; std::vector<int> idx[4];
-    for (int i = 0; i < n; i++) { ok[i] = 0; if (items[i].kind >= 0 && items[i].kind <= 3) idx[items[i].kind].push_back(i); }
-    for (int k = 0; k < 4; k++) { if (idx[k].empty()) continue; Group g; g.kind = (CircuitKind)k; g.path = key_path(g.kind, false); g.idx = idx[k]; const size_t m = g.idx.size();
-      g.ps.resize(m); g.parsed.resize(m); g.res.assign(m, 0);
-      for (size_t j = 0; j < m; j++) {
-        const zk_verify_item &it = items[g.idx[j]];
-        g.parsed[j] = it.proof && strnlen(it.proof, 512) == 512 && proof_from_hex(it.proof, g.ps[j]);
-        if (!g.parsed[j]) memset(&g.ps[j], 0, sizeof(Proof));
-        std::vector<Fe32> in = pack_public_bits(public_bits(g.kind, it.args, it.value_s)); g.ni = in.size(); g.inputs.insert(g.inputs.end(), in.begin(), in.end()); }
-      groups.push_back(std::move(g)); }
+    for (int i = 0; i < n; i++) { ok[i] = 0; if (recs[i].kind <= 3) idx[recs[i].kind].push_back(i); }
+    for (int k = 0; k < 4; k++) { if (idx[k].empty()) continue; Group g; g.kind = (CircuitKind)k; g.path = key_path(g.kind, false); g.idx = std::move(idx[k]);
+      g.ni = record_num_inputs(k); g.res.assign(g.idx.size(), 0); groups.push_back(std::move(g)); }
+    const bool one_kind = groups.size() == 1 && groups[0].idx.size() == (size_t)n;       // (a block of one kind is staged with one copy)
     bool any_eq = false;
     if (gpu_available()) {
       try {
@@ -1156,25 +1233,62 @@ int verifyBlock(const zk_verify_item *items, int n, unsigned char *ok) {
         for (Group &g : groups) {
           const size_t m = g.idx.size(); if (m < RLC_MIN_RECORDS) continue;
           std::shared_ptr<PreparedVerifyingKey> vk = vk_for_path(g.path); if (vk->vk.IC.size() != g.ni + 1) continue;   // (strong IC: verify_group rejects the group)
-          std::vector<uint8_t> w(16 * m); fresh_weights(w.data(), m);
-          if (!rlc_part(g.path, g.ps.data(), g.inputs.data(), g.ni, m, w.data(), true, g.part) || !g.part.in_eq || g.part.s_acc.is_inf() || g.part.s_c.is_inf()) continue;
-          lhs = lhs * rlc_lhs(*vk, g.part.prod, g.part.s_acc, g.part.s_c); rhs = rhs * rlc_rhs(*vk, g.part.s); g.in_eq = true; any_eq = true;
+          std::vector<uint8_t> w(16 * m); { HostSpan span("host.weights"); fresh_weights(w.data(), m); }
+          if (!rlc_part_records(g.path, g.kind, recs, one_kind ? nullptr : g.idx.data(), m, w.data(), true, g.part) || !g.part.in_eq || g.part.s_acc.is_inf() ||
+              g.part.s_c.is_inf()) continue;
+          HostSpan span("host.closing"); lhs = lhs * rlc_lhs(*vk, g.part.prod, g.part.s_acc, g.part.s_c); rhs = rhs * rlc_rhs(*vk, g.part.s); g.in_eq = true; any_eq = true;
         }
         if (any_eq) {
-          const bool pass = host::final_exponentiation(lhs) == rhs; (pass ? g_rlc_passed : g_rlc_failed).fetch_add(1);
-          if (pass) { for (Group &g : groups) if (g.in_eq) { decide_from_flags(g.path, g.part, g.ps.data(), g.parsed.data(), g.inputs.data(), g.ni, g.idx.size(), g.res.data()); g.decided = true; } }
+          bool pass; { HostSpan span("host.closing"); pass = host::final_exponentiation(lhs) == rhs; } (pass ? g_rlc_passed : g_rlc_failed).fetch_add(1);
+          if (pass) { for (Group &g : groups) if (g.in_eq) { decide_from_flags(g.path, g.part, nullptr, g.ni, g.idx.size(), g.res.data()); g.decided = true; } }
           else any_eq = false;
         }
       } catch (const std::exception &e) {
-        fprintf(stderr, "libzkgpu: verifyBlock: block check failed (%s); deciding proof by proof\n", e.what());
+        fprintf(stderr, "libzkgpu: %s: block check failed (%s); deciding proof by proof\n", who, e.what());
         any_eq = false; for (Group &g : groups) g.decided = false;
       }
     }
     if (!any_eq) g_rlc_per_proof.fetch_add(1);
-    for (Group &g : groups) if (!g.decided) verify_group(g.kind, g.ps.data(), g.parsed.data(), g.inputs.data(), g.ni, g.idx.size(), g.res.data());
+    for (Group &g : groups) if (!g.decided) {
+      std::vector<Proof> ps; std::vector<uint8_t> parsed; std::vector<Fe32> inputs;
+      records_for_per_proof(recs, one_kind ? nullptr : g.idx.data(), g.idx.size(), g.kind, ps, parsed, inputs, true);
+      verify_group(g.kind, ps.data(), parsed.data(), inputs.data(), g.ni, g.idx.size(), g.res.data());
+    }
     int accepted = 0;
     for (Group &g : groups) for (size_t j = 0; j < g.idx.size(); j++) { ok[g.idx[j]] = g.res[j]; accepted += g.res[j]; }
     return accepted;
+  }
+  catch (const std::exception &e) {
+    zkgpu_set_error(e.what()); fprintf(stderr, "libzkgpu: %s: %s\n", who, e.what());
+    for (int i = 0; i < n; i++) ok[i] = 0;
+    return -1;
+  }
+  catch (...) { for (int i = 0; i < n; i++) ok[i] = 0; return -1; }
+}
+}  // namespace
+
+int verifyBlockRecords(const zk_block_record *recs, int n, unsigned char *ok) {
+  if (n < 0 || (n && (!recs || !ok))) return -1;
+  return verify_block_records(recs, n, ok, "verifyBlockRecords");
+}
+// verifyBlock (include/zk_block.h), the entry that takes strings: every item becomes a record — an argument through blob256_from_hex / blob160_from_hex, so every
+// odd string keeps its meaning, the blob reversed into the hash's byte order; the proof's 512 characters copied, or left as NULs (no hex digits: the record does
+// not parse) where the string is missing or shorter — and the block is decided as verifyBlockRecords decides it.
+int verifyBlock(const zk_verify_item *items, int n, unsigned char *ok) {
+  if (n < 0 || (n && (!items || !ok))) return -1;
+  try {
+    std::vector<zk_block_record> recs((size_t)n);                                         // (value-initialised: all zero)
+    for (int i = 0; i < n; i++) {
+      const zk_verify_item &it = items[i]; zk_block_record &r = recs[i]; r.kind = it.kind >= 0 && it.kind <= 3 ? (uint8_t)it.kind : 0xff; r.value_s = it.value_s;
+      if (it.proof && strnlen(it.proof, 512) == 512) memcpy(r.proof, it.proof, 512);
+      if (r.kind == 0xff) continue;
+      const int n_args = r.kind == ZK_KIND_SEND ? 4 : r.kind == ZK_KIND_DEPOSIT ? 6 : 3;
+      for (int a = 0; a < n_args; a++) {
+        if (r.kind == ZK_KIND_DEPOSIT && a == 1) { const Blob160 b = blob160_from_hex(it.args[a] ? it.args[a] : ""); for (int k = 0; k < 20; k++) r.args[a][k] = b.b[19 - k]; }
+        else { const Blob256 b = blob256_from_hex(it.args[a] ? it.args[a] : ""); for (int k = 0; k < 32; k++) r.args[a][k] = b.b[31 - k]; }
+      }
+    }
+    return verify_block_records(recs.data(), n, ok, "verifyBlock");
   }
   catch (const std::exception &e) {
     zkgpu_set_error(e.what()); fprintf(stderr, "libzkgpu: verifyBlock: %s\n", e.what());
@@ -1183,6 +1297,52 @@ int verifyBlock(const zk_verify_item *items, int n, unsigned char *ok) {
   }
   catch (...) { for (int i = 0; i < n; i++) ok[i] = 0; return -1; }
 }
+
+// zkgpu_verify_batch_rlc for records of ONE kind (include/zkgpu.h)
+static int records_one_kind(const zk_block_record *recs, size_t n) {
+  if (!recs || !n || recs[0].kind > 3) return -1;
+  for (size_t i = 1; i < n; i++) if (recs[i].kind != recs[0].kind) return -1;
+  return recs[0].kind;
+}
+int zkgpu_verify_records_rlc(const char *vk_path, const zk_block_record *recs, size_t n, const uint8_t *weights, uint8_t *ok, uint32_t *by_equation) { return guarded([&] {
+  if (!vk_path || (!recs && n) || !ok) return ZKGPU_ERR_ARG;
+  if (by_equation) *by_equation = 0;
+  if (!n) return ZKGPU_OK;
+  const int kind = records_one_kind(recs, n); if (kind < 0) { zkgpu_set_error("the records are not of one known kind"); return ZKGPU_ERR_ARG; }
+  std::vector<uint8_t> w; if (!weights_from(weights, n, w)) { zkgpu_set_error("a weight is 0"); return ZKGPU_ERR_ARG; }
+  std::shared_ptr<BatchVerifier> v = gpu_verifier_for_path(vk_path); const size_t ni = record_num_inputs(kind);
+  if (v->num_inputs() != ni) { for (size_t i = 0; i < n; i++) ok[i] = 0; g_rlc_per_proof.fetch_add(1); return ZKGPU_OK; }   // strong IC
+  return rlc_engine_call(vk_path, nullptr, ni, n, ok, by_equation, [&](RlcPart &p) { return rlc_part_records(vk_path, (CircuitKind)kind, recs, nullptr, n, w.data(), false, p); },
+      [&] { std::vector<Proof> ps; std::vector<uint8_t> parsed; std::vector<Fe32> in; records_for_per_proof(recs, nullptr, n, (CircuitKind)kind, ps, parsed, in, false);
+            per_proof_verdicts(vk_path, *v, ps.data(), parsed.data(), in.data(), ni, n, ok); }); }); }
+// test entries.  zkgpu_test_ingest_records: the converter's three arrays for records of one kind, from k_ingest_records (device = 1) or from records_to_host
+// (device = 0: no device needed).  zkgpu_test_records_rlc: the equation through the device path from records, whatever their count: 1 / 0 as
+// zkgpu_test_verify_rlc_device, its GT value and the device's integer sums.  zkgpu_test_rlc_sums_host: the host loop's sums.
+int zkgpu_test_ingest_records(const zk_block_record *recs, size_t n, int device, uint8_t *items_out, uint8_t *inputs_out, size_t *n_inputs_out, uint8_t *parsed_out) {
+  auto body = [&] {
+    if (!n_inputs_out) return ZKGPU_ERR_ARG; *n_inputs_out = 0;
+    if (!n) return ZKGPU_OK;
+    const int kind = records_one_kind(recs, n); if (kind < 0 || !items_out || !inputs_out || !parsed_out) { zkgpu_set_error("the records are not of one known kind"); return ZKGPU_ERR_ARG; }
+    std::vector<Proof> ps; std::vector<uint8_t> parsed; std::vector<Fe32> in;
+    if (device) records_to_host_by_device(recs, nullptr, n, (CircuitKind)kind, ps, parsed, in, false); else records_to_host(recs, nullptr, n, (CircuitKind)kind, ps, parsed, in);
+    *n_inputs_out = record_num_inputs(kind); memcpy(items_out, ps.data(), n * sizeof(Proof)); memcpy(inputs_out, in.data(), in.size() * sizeof(Fe32)); memcpy(parsed_out, parsed.data(), n);
+    return ZKGPU_OK; };
+  return device ? guarded(body) : guarded_host(body); }
+int zkgpu_test_records_rlc(const char *vk_path, const zk_block_record *recs, size_t n, const uint8_t *weights, uint8_t *gt, uint64_t *sums_out) {
+  int res = 0; int rc = guarded([&] {
+    if (!vk_path || !recs || !n) return ZKGPU_ERR_ARG;
+    const int kind = records_one_kind(recs, n); if (kind < 0) { zkgpu_set_error("the records are not of one known kind"); return ZKGPU_ERR_ARG; }
+    std::vector<uint8_t> w; if (!weights_from(weights, n, w)) return ZKGPU_ERR_ARG;
+    if (vk_for_path(vk_path)->vk.IC.size() != record_num_inputs(kind) + 1) { zkgpu_set_error("the key's input count is not the kind's"); return ZKGPU_ERR_ARG; }
+    RlcPart p;
+    if (!rlc_part_records(vk_path, (CircuitKind)kind, recs, nullptr, n, w.data(), false, p)) { zkgpu_set_error("the key fails the subgroup checks of the block equation"); return ZKGPU_ERR_ARG; }
+    const host::HFq12 g = host::final_exponentiation(rlc_lhs(*vk_for_path(vk_path), p.prod, p.s_acc, p.s_c)); if (gt) gt_bytes(g, gt);
+    if (sums_out) memcpy(sums_out, p.sums.data(), p.sums.size() * sizeof(uint64_t));
+    res = g == rlc_rhs(*vk_for_path(vk_path), p.s) ? 1 : 0; return ZKGPU_OK; });
+  return rc == ZKGPU_OK ? res : rc; }
+int zkgpu_test_rlc_sums_host(const uint8_t *inputs, size_t n_inputs, const uint8_t *weights, const uint8_t *flags, size_t n, uint64_t *sums_out) { return guarded_host([&] {
+  if ((n && (!weights || !flags || (n_inputs && !inputs))) || !sums_out) return ZKGPU_ERR_ARG;
+  rlc_int_sums((const Fe32 *)inputs, n_inputs, weights, flags, n, sums_out); return ZKGPU_OK; }); }
 
 // ---- the resident commitment tree (DESIGN.md "Commitment tree"; include/zkgpu.h, include/zk_tree.h) ---------------------------------------------------------
 zkgpu_tree *zkgpu_tree_create(int depth) {

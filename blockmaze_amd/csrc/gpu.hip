@@ -2,6 +2,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
+#include <chrono>
 #include <cstring>
 #include <map>
 #include <vector>
@@ -209,6 +210,10 @@ static StageTimer g_timer;
 Stage::Stage(const char *n, hipStream_t st) : id(g_timer.begin(n, st ? st : gpu().stream)) {}
 Stage::~Stage() { g_timer.end(id); }
 bool profiling_enabled() { return g_timer.enabled; }
+void profile_add_host(const char *name, double ms) { if (!g_timer.enabled) return; std::lock_guard<std::mutex> lk(g_timer.mu); auto &e = g_timer.acc[name]; e.first += ms; e.second++; }
+static double host_now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+HostSpan::HostSpan(const char *n) : name(n), on(g_timer.enabled), t0(on ? host_now_ms() : 0.0) {}
+HostSpan::~HostSpan() { if (on) profile_add_host(name, host_now_ms() - t0); }
 void profile_enable(bool on) { g_timer.collect(); g_timer.enabled = on; g_timer.acc.clear(); }
 std::string profile_report() { g_timer.collect(); std::string o = "{"; bool first = true;
   for (auto &kv : g_timer.acc) {

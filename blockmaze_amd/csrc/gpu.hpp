@@ -141,8 +141,33 @@ class BlockVerifier {
   // weights: n x 16 bytes (little-endian 128-bit r_i).  flags[i]: 1 in the equation, 0 rejected by the screen, 2 input accumulator at infinity.  prod = the product of
   // Miller(A_i, B_i)^{r_i}, sum_c = the sum of r_i C_i, both over the records flagged 1
   void run(const void *proofs_mont, const Fe32 *inputs_canonical, const uint8_t *weights, size_t n, uint8_t *flags, host::HFq12 &prod, host::HG1 &sum_c);
+  // run() on arrays that already lie in device memory (RecordIngest below).  parsed_dev: one byte per record, ANDed into the screen — an unparsed record gets flag 0
+  // whatever its zeroed points are.  sums: (num_inputs() + 1) x 7 words, the integers sum r_i and sum r_i x_ij over the records flagged 1 (k_block_scalar_sums), what
+  // rlc_int_sums makes on the host.  The call's workspace is kept by the verifier and grown on demand: one caller at a time (the device mutex).
+  void run_resident(const void *items_dev, const Fe32 *inputs_dev, const uint8_t *parsed_dev, const uint8_t *weights, size_t n, uint8_t *flags, host::HFq12 &prod,
+      host::HG1 &sum_c, uint64_t *sums);
+  struct Impl; std::unique_ptr<Impl> impl;
+ private:
+  void run_resident_unsynced(const void *items_dev, const Fe32 *inputs_dev, const uint8_t *parsed_dev, const uint8_t *weights, size_t n, uint8_t *flags,
+      host::HFq12 &prod, host::HG1 &sum_c, uint64_t *sums);
+};
+// Device ingest of block records (gpu_verify_ingest.hip; include/zk_records.h): n records of ONE kind, 720 bytes each, written by the caller into stage(n) — pinned
+// memory, kept and grown —, then run(): one upload and k_ingest_records on the main stream, no synchronisation.  What it leaves in device memory is what
+// BlockVerifier::run uploads: 256-byte proof records (affine, Montgomery; all zero where the 512 characters are not a proof), record_num_inputs(kind) canonical field elements a
+// record, and a `parsed` byte.  strict: a coordinate of q or more is not a proof (ZK_STRICT_PROOF_ENCODING).  One caller at a time (the device mutex).
+size_t record_num_inputs(int kind);   // 4 / 5 / 6 / 4 packed inputs for mint / send / deposit / redeem (832 / 1,024 / 1,440 / 832 bits), 0 for an unknown kind
+class RecordIngest {
+ public:
+  RecordIngest(); ~RecordIngest();
+  uint8_t *stage(size_t n);
+  void run(size_t n, int kind, bool strict);
+  const void *items_dev() const; const Fe32 *inputs_dev() const; const uint8_t *parsed_dev() const;
+  void download(size_t first, size_t count, void *items, Fe32 *inputs, uint8_t *parsed);   // any of the three may be null; synchronises the main stream
   struct Impl; std::unique_ptr<Impl> impl;
 };
+// k_block_scalar_sums on the main stream: out = (n_inputs + 1) x 7 words in device memory; partials: block_scalar_sums_scratch(n_inputs) words of scratch
+size_t block_scalar_sums_scratch(size_t n_inputs);
+void block_scalar_sums_dev(const Fe32 *inputs, size_t n_inputs, const uint8_t *weights, const uint8_t *flags, size_t n, uint64_t *partials, uint64_t *out);
 
 // The commitment tree of the deposit circuit, resident in HBM (gpu_tree.hip): an append-only SHA-256 Merkle tree of depth 1..32 with all-zero unseen leaves,
 // the tree of notes.cpp:tree_levels.  Leaves, siblings and roots are 32-byte blobs in blob byte order.  One mutex per tree: append, root, path, find and snapshot
@@ -248,5 +273,8 @@ uint64_t general_path_repeats();   // how often a fast MSM path raised its flag 
 void note_general_path_repeat();
 // per-stage device timing (HIP events on the compute stream); report = JSON object {stage: {ms_total, count}}
 void profile_enable(bool on); std::string profile_report();
+// host work beside the device stages of the same report (wall-clock ms under `name`); a no-op while profiling is off
+void profile_add_host(const char *name, double ms);
+struct HostSpan { const char *name; bool on; double t0; explicit HostSpan(const char *n); ~HostSpan(); HostSpan(const HostSpan &) = delete; };
 
 }  // namespace zk

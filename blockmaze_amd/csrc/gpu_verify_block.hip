@@ -104,7 +104,14 @@ static __global__ void __launch_bounds__(64) k_block_reduce(const Fq12 *__restri
   XYZZ<Fq> p = ua ? p_in[a] : XYZZ<Fq>::inf(); if (ub) p.add_inl(p_in[b]); p_out[i] = p;
 }
 
-struct BlockVerifier::Impl { size_t n_inputs = 0; DevBuf<uint8_t> tables; Affine<Fq> ic0; BlockConsts K; };
+// the screen of a call from records: a record whose 512 characters are not a proof is rejected whatever its zeroed points are
+static __global__ void __launch_bounds__(256) k_block_and_parsed(const uint8_t *__restrict__ parsed, uint32_t n, uint8_t *__restrict__ flag) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x; if (i < n && !parsed[i]) flag[i] = 0;
+}
+
+// run_resident's workspace: device arrays for `cap` records, and pinned memory for the weights on their way in and the results on their way out
+struct BlockWorkspace { size_t cap = 0; DevBuf<uint8_t> w, fl, f, c, f2, c2, sums; PinnedBuf<Fe32> hw, hres; };
+struct BlockVerifier::Impl { size_t n_inputs = 0; DevBuf<uint8_t> tables; Affine<Fq> ic0; BlockConsts K; BlockWorkspace ws; };
 
 template <class T, class H> static T bk_to_dev(const H &h) { static_assert(sizeof(T) == sizeof(H), "layout"); T t; memcpy(&t, &h, sizeof(T)); return t; }
 
@@ -148,6 +155,52 @@ void BlockVerifier::run(const void *proofs_mont, const Fe32 *inputs_canonical, c
   fl.download(flags, n);
   Fq12 pd; HIP_CHECK(hipMemcpy(&pd, fa, sizeof pd, hipMemcpyDeviceToHost)); memcpy(&prod, &pd, sizeof pd);
   XYZZ<Fq> p; HIP_CHECK(hipMemcpy(&p, ca, sizeof p, hipMemcpyDeviceToHost));
+  host::HFq X, Y, ZZ, ZZZ; memcpy(X.l, p.X.l, 32); memcpy(Y.l, p.Y.l, 32); memcpy(ZZ.l, p.ZZ.l, 32); memcpy(ZZZ.l, p.ZZZ.l, 32);
+  sum_c = host::HG1::from_xyzz(X, Y, ZZ, ZZZ);
+  for (size_t k = 0; k < n; k++) if (flags[k] > 2) throw GpuError("block verify: a flag did not arrive");
+}
+
+void BlockVerifier::run_resident(const void *items_dev, const Fe32 *inputs_dev, const uint8_t *parsed_dev, const uint8_t *weights, size_t n, uint8_t *flags,
+    host::HFq12 &prod, host::HG1 &sum_c, uint64_t *sums) {
+  if (!n || n > (1u << 26)) throw GpuError("block verify: record count");
+  try { run_resident_unsynced(items_dev, inputs_dev, parsed_dev, weights, n, flags, prod, sum_c, sums); }
+  catch (...) { (void)hipStreamSynchronize(gpu().stream); throw; }             // (the pinned weights and results are the next caller's as soon as this one leaves)
+}
+void BlockVerifier::run_resident_unsynced(const void *items_dev, const Fe32 *inputs_dev, const uint8_t *parsed_dev, const uint8_t *weights, size_t n, uint8_t *flags,
+    host::HFq12 &prod, host::HG1 &sum_c, uint64_t *sums) {
+  Impl &d = *impl; BlockWorkspace &ws = d.ws; hipStream_t s = gpu().stream; const size_t rows = d.n_inputs + 1, sum_bytes = rows * 7 * sizeof(uint64_t);
+  if (n > ws.cap) {
+    const size_t cap = n + n / 4 + 64, half = (cap + 1) / 2;
+    ws.w = DevBuf<uint8_t>(cap * 16); ws.fl = DevBuf<uint8_t>(cap); ws.f = DevBuf<uint8_t>(cap * sizeof(Fq12)); ws.c = DevBuf<uint8_t>(cap * sizeof(XYZZ<Fq>));
+    ws.f2 = DevBuf<uint8_t>(half * sizeof(Fq12)); ws.c2 = DevBuf<uint8_t>(half * sizeof(XYZZ<Fq>));
+    ws.sums = DevBuf<uint8_t>((block_scalar_sums_scratch(d.n_inputs) + rows * 7) * sizeof(uint64_t));
+    ws.hw = PinnedBuf<Fe32>(cap * 16 / sizeof(Fe32) + 1); ws.hres = PinnedBuf<Fe32>((cap + sizeof(Fq12) + sizeof(XYZZ<Fq>) + sum_bytes) / sizeof(Fe32) + 4); ws.cap = cap;
+  }
+  memcpy(ws.hw.get(), weights, n * 16); upload_async(ws.w.get(), ws.hw.get(), n * 16);
+  HIP_CHECK(hipMemsetAsync(ws.fl.get(), 0xff, n, s));
+  uint8_t *fa = ws.f.get(), *ca = ws.c.get(), *fb = ws.f2.get(), *cb = ws.c2.get();
+  { Stage st("verify.block");
+    const uint32_t nb = cdiv(n, 64);
+    hipLaunchKernelGGL(k_block_records, dim3(2 * nb), dim3(64), 0, s, (const VerifyItem *)items_dev, (const Fr *)inputs_dev, (uint32_t)d.n_inputs,
+        (const Affine<Fq> *)d.tables.get(), d.ic0, (const uint4 *)ws.w.get(), d.K, (uint32_t)n, nb, (Fq12 *)ws.f.get(), (XYZZ<Fq> *)ws.c.get(), ws.fl.get());
+    hipLaunchKernelGGL(k_block_and_parsed, dim3(cdiv(n, 256)), dim3(256), 0, s, parsed_dev, (uint32_t)n, ws.fl.get());
+    size_t m = n; bool first = true;
+    while (first || m > 1) {                                                   // the tree of run()
+      const size_t h = (m + 1) / 2;
+      hipLaunchKernelGGL(k_block_reduce, dim3(cdiv(h, 64)), dim3(64), 0, s, (const Fq12 *)fa, (const XYZZ<Fq> *)ca, first ? (const uint8_t *)ws.fl.get() : nullptr,
+          (uint32_t)m, (Fq12 *)fb, (XYZZ<Fq> *)cb);
+      std::swap(fa, fb); std::swap(ca, cb); m = h; first = false;
+    } }
+  uint64_t *partials = (uint64_t *)ws.sums.get(), *sums_dev = partials + block_scalar_sums_scratch(d.n_inputs);
+  { Stage st("verify.sums"); block_scalar_sums_dev(inputs_dev, d.n_inputs, ws.w.get(), ws.fl.get(), n, partials, sums_dev); }   // (behind the flags)
+  HIP_CHECK(hipGetLastError());
+  // one pinned block for everything that comes back: the product, the sum, the integer sums (each 32-byte aligned), then the flags
+  uint8_t *hr = (uint8_t *)ws.hres.get(), *h_prod = hr, *h_sum = hr + sizeof(Fq12), *h_sums = h_sum + sizeof(XYZZ<Fq>), *h_fl = h_sums + (sum_bytes + 31) / 32 * 32;
+  HIP_CHECK(hipMemcpyAsync(h_prod, fa, sizeof(Fq12), hipMemcpyDeviceToHost, s)); HIP_CHECK(hipMemcpyAsync(h_sum, ca, sizeof(XYZZ<Fq>), hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(h_sums, sums_dev, sum_bytes, hipMemcpyDeviceToHost, s)); HIP_CHECK(hipMemcpyAsync(h_fl, ws.fl.get(), n, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));                                          // (a fault surfaces in the call that caused it)
+  memcpy(flags, h_fl, n); memcpy(&prod, h_prod, sizeof(Fq12)); memcpy(sums, h_sums, sum_bytes);
+  XYZZ<Fq> p; memcpy(&p, h_sum, sizeof p);
   host::HFq X, Y, ZZ, ZZZ; memcpy(X.l, p.X.l, 32); memcpy(Y.l, p.Y.l, 32); memcpy(ZZ.l, p.ZZ.l, 32); memcpy(ZZZ.l, p.ZZZ.l, 32);
   sum_c = host::HG1::from_xyzz(X, Y, ZZ, ZZZ);
   for (size_t k = 0; k < n; k++) if (flags[k] > 2) throw GpuError("block verify: a flag did not arrive");

@@ -125,6 +125,10 @@ std::unique_ptr<BatchVerifier> make_batch_verifier(const VerifyingKeyHost &vk);
 bool rlc_key_ok(const PreparedVerifyingKey &pvk);    // [r]gamma = [r]delta = O and alpha_g1_beta_g2^r = 1: the key may be checked with the equation
 // S_acc = s IC[0] + sum_j (sum_i r_i x_ij) IC[j+1] over the records flagged 1; s_out = s mod r, canonical
 host::HG1 rlc_acc_sum(const PreparedVerifyingKey &pvk, const Fe32 *inputs, size_t ni, const uint8_t *weights, const uint8_t *flags, size_t n, uint64_t s_out[4]);
+// its two halves: the integers sum r_i (acc[0..6]) and sum r_i x_ij (acc[7 (j + 1) ..]) over the records flagged 1, seven 64-bit limbs each — what the device makes
+// for a call from records (k_block_scalar_sums) —, and the tail both roads share: the reduction modulo r and the ni + 1 scalar multiplications of IC
+void rlc_int_sums(const Fe32 *inputs, size_t ni, const uint8_t *weights, const uint8_t *flags, size_t n, uint64_t *acc /* (ni + 1) x 7 */);
+host::HG1 rlc_acc_from_sums(const PreparedVerifyingKey &pvk, const uint64_t *acc, size_t ni, uint64_t s_out[4]);
 // prod * Miller(-S_acc, gamma) * Miller(-S_C, delta), a point at infinity contributing 1 (before the final exponentiation)
 host::HFq12 rlc_lhs(const PreparedVerifyingKey &pvk, const host::HFq12 &prod, const host::HG1 &s_acc, const host::HG1 &s_c);
 host::HFq12 rlc_rhs(const PreparedVerifyingKey &pvk, const uint64_t s[4]);   // alpha_g1_beta_g2^s
@@ -137,6 +141,7 @@ static_assert(sizeof(Proof) == 256, "proof record");
 // proof <-> the 512-hex-character form of the cgo wrappers (sendcgo.cpp:113-188, :388-448)
 std::string proof_to_hex(const Proof &p);
 bool proof_from_hex(const char *hex, Proof &p);   // reads exactly 512 characters; false on a non-hex character
+bool proof_encoding_strict();                     // ZK_STRICT_PROOF_ENCODING is set: a coordinate of q or more is not a proof (read once)
 Proof default_proof();                            // (G1::one, G2::one, G1::one) — r1cs_gg_ppzksnark.hpp:309-315
 
 // host-only self-test of the hand-over's block classifiers (scalar against AVX2 forms)

@@ -166,10 +166,9 @@ bool rlc_key_ok(const PreparedVerifyingKey &pvk) {
   uint64_t r[4]; r_limbs(r); const VerifyingKeyHost &vk = pvk.vk;
   return g2_of(vk.gamma_g2).mul(r).is_inf() && g2_of(vk.delta_g2).mul(r).is_inf() && fq12_pow(vk.alpha_g1_beta_g2, r, 4) == HFq12::one();
 }
-host::HG1 rlc_acc_sum(const PreparedVerifyingKey &pvk, const Fe32 *inputs, size_t ni, const uint8_t *weights, const uint8_t *flags, size_t n, uint64_t s_out[4]) {
-  const VerifyingKeyHost &vk = pvk.vk; if (vk.IC.size() != ni + 1) throw std::runtime_error("block verify: input count");
+void rlc_int_sums(const Fe32 *inputs, size_t ni, const uint8_t *weights, const uint8_t *flags, size_t n, uint64_t *acc) {
   // the integers s = sum r_i and c_j = sum r_i x_ij in 7 limbs each (128 + 256 bits a product, fewer than 2^31 records), reduced modulo r once at the end
-  std::vector<uint64_t> acc((ni + 1) * 7, 0);
+  for (size_t k = 0; k < (ni + 1) * 7; k++) acc[k] = 0;
   auto add_at = [](uint64_t *a, int k, u128 v) { for (; v && k < 7; k++) { const u128 s = (u128)a[k] + (uint64_t)v; a[k] = (uint64_t)s; v = (v >> 64) + (s >> 64); } };
   for (size_t i = 0; i < n; i++) {
     if (flags[i] != 1) continue;
@@ -177,11 +176,19 @@ host::HG1 rlc_acc_sum(const PreparedVerifyingKey &pvk, const Fe32 *inputs, size_
     for (size_t j = 0; j < ni; j++) { uint64_t x[4]; memcpy(x, &inputs[i * ni + j], 32);
       for (int a = 0; a < 2; a++) for (int b = 0; b < 4; b++) add_at(&acc[(j + 1) * 7], a + b, (u128)w[a] * x[b]); }
   }
+}
+host::HG1 rlc_acc_from_sums(const PreparedVerifyingKey &pvk, const uint64_t *acc, size_t ni, uint64_t s_out[4]) {
+  const VerifyingKeyHost &vk = pvk.vk; if (vk.IC.size() != ni + 1) throw std::runtime_error("block verify: input count");
   const HFr two64 = HFr::from_u64(1ull << 32) * HFr::from_u64(1ull << 32);
   auto reduce = [&](const uint64_t *a, uint64_t out[4]) { HFr v = HFr::zero(); for (int k = 6; k >= 0; k--) v = v * two64 + HFr::from_u64(a[k]); v = v.from_mont(); memcpy(out, v.l, 32); };
   reduce(&acc[0], s_out); HG1 S = g1_of(vk.IC[0]).mul(s_out);
   for (size_t j = 0; j < ni; j++) { uint64_t c[4]; reduce(&acc[(j + 1) * 7], c); if (!is_zero_raw(&vk.IC[j + 1], sizeof(G1AffineRaw))) S = S.add(g1_of(vk.IC[j + 1]).mul(c)); }
   return S;
+}
+host::HG1 rlc_acc_sum(const PreparedVerifyingKey &pvk, const Fe32 *inputs, size_t ni, const uint8_t *weights, const uint8_t *flags, size_t n, uint64_t s_out[4]) {
+  if (pvk.vk.IC.size() != ni + 1) throw std::runtime_error("block verify: input count");
+  std::vector<uint64_t> acc((ni + 1) * 7, 0); rlc_int_sums(inputs, ni, weights, flags, n, acc.data());
+  return rlc_acc_from_sums(pvk, acc.data(), ni, s_out);
 }
 host::HFq12 rlc_lhs(const PreparedVerifyingKey &pvk, const host::HFq12 &prod, const host::HG1 &s_acc, const host::HG1 &s_c) {
   HFq12 m = prod; HFq x, y;
@@ -237,8 +244,9 @@ std::string proof_to_hex(const Proof &p) {
   put_hex_fq(o, p.C.y);
   return o;
 }
+bool proof_encoding_strict() { static const bool strict = [] { const char *e = getenv("ZK_STRICT_PROOF_ENCODING"); return e && *e && *e != '0'; }(); return strict; }
 bool proof_from_hex(const char *hex, Proof &p) {
-  static const bool strict = [] { const char *e = getenv("ZK_STRICT_PROOF_ENCODING"); return e && *e && *e != '0'; }();
+  static const bool strict = proof_encoding_strict();
   Fe32 v[8];
   for (int k = 0; k < 8; k++) {
     HFq c = HFq::zero();

@@ -218,6 +218,50 @@ def verify_rlc_counters():
     """(block equations that held, equations that failed, calls decided proof by proof), process-wide"""
     out = (ctypes.c_uint64 * 3)(); _check(lib().zkgpu_verify_rlc_counters(out)); return tuple(int(x) for x in out)
 
+# ---- blocks as records (include/zk_records.h) -----------------------------------------------------------------------------
+# one record = 720 bytes, no padding: the layout of zk_block_record (tests/test_block_records_cpu.py compares it with a C compiler's)
+RECORD_DTYPE = np.dtype([("kind", "u1"), ("reserved", "u1", (7,)), ("value_s", "<u8"), ("proof", "u1", (512,)), ("args", "u1", (6, 32))])
+assert RECORD_DTYPE.itemsize == 720
+def records_from_items(items):
+    """items as Zk.VerifyBlock takes them — (kind, proof hex, [big-endian byte strings in the order of the kind's verify symbol], value_s) — as one array of
+    zk_block_record.  An argument keeps the meaning Zk.hx + blob256_from_hex give it: its last 32 (pk: 20) bytes, zero-extended on the left; a proof shorter than
+    512 characters is padded with NULs (it does not parse), a longer one is cut as strnlen(proof, 512) cuts it.  One bytes object per item, no loop per byte."""
+    import struct
+    def arg(a, w): a = bytes(a)[-w:]; return (a.rjust(w, b"\0")).ljust(32, b"\0")
+    out = []
+    for kind, proof, args, value_s in items:
+        k = KIND[kind] if isinstance(kind, str) else int(kind); pb = (proof.encode() if isinstance(proof, str) else bytes(proof or b""))[:512].split(b"\0")[0].ljust(512, b"\0")
+        ab = b"".join(arg(a, 20 if (k == 2 and j == 1) else 32) for j, a in enumerate(args[:6])).ljust(192, b"\0")
+        out.append(struct.pack("<B7xQ", k if 0 <= k <= 255 else 255, int(value_s or 0) & 0xFFFFFFFFFFFFFFFF) + pb + ab)
+    return np.frombuffer(b"".join(out), dtype=RECORD_DTYPE).copy() if out else np.zeros(0, dtype=RECORD_DTYPE)
+def _recs(recs):
+    recs = np.ascontiguousarray(recs, dtype=RECORD_DTYPE); return recs, recs.ctypes.data_as(ctypes.c_void_p), int(recs.shape[0])
+def ingest_records(recs, device=True):
+    """zkgpu_test_ingest_records: records of one kind -> (items (n, 8, 4) uint64 Montgomery words, inputs (n, n_inputs, 4) uint64 canonical, parsed (n,) uint8),
+    from k_ingest_records (device=True) or from the host converter (device=False: needs no device)"""
+    recs, ptr, n = _recs(recs); items = np.zeros((max(1, n), 8, 4), dtype=np.uint64); inputs = np.zeros((max(1, n), 6, 4), dtype=np.uint64); parsed = np.zeros(max(1, n), dtype=np.uint8)
+    ni = ctypes.c_size_t(0); _check(lib().zkgpu_test_ingest_records(ptr, ctypes.c_size_t(n), int(bool(device)), _bytes(items), _bytes(inputs), ctypes.byref(ni), _bytes(parsed)))
+    k = int(ni.value); return items[:n], inputs.reshape(-1)[:n * k * 4].reshape(n, k, 4).copy(), parsed[:n]
+def _weights(weights, n):
+    wb = None if weights is None else b"".join(int(r).to_bytes(16, "little") for r in weights); assert wb is None or len(wb) == 16 * n; return wb
+def verify_records_rlc(vk_path, recs, weights=None):
+    """zkgpu_verify_records_rlc: verify_batch_rlc for records of one kind -> (list of n booleans, True if the equation decided the call)"""
+    recs, ptr, n = _recs(recs); ok = (ctypes.c_uint8 * max(1, n))(); by = ctypes.c_uint32(0)
+    _check(lib().zkgpu_verify_records_rlc(vk_path.encode(), ptr, ctypes.c_size_t(n), _weights(weights, n), ok, ctypes.byref(by))); return [bool(ok[i]) for i in range(n)], bool(by.value)
+def _ints448(a): return [sum(int(w) << (64 * k) for k, w in enumerate(row)) for row in np.asarray(a, dtype=np.uint64).reshape(-1, 7)]
+def records_rlc_equation(vk_path, recs, weights):
+    """zkgpu_test_records_rlc: the block equation from records through the device path -> (holds, 384-byte GT value, the device's integer sums [sum r_i, sum r_i x_i0, ...])"""
+    recs, ptr, n = _recs(recs); gt = (ctypes.c_uint8 * 384)(); sums = np.zeros(7 * 7, dtype=np.uint64); ni = {0: 4, 1: 5, 2: 6, 3: 4}[int(recs["kind"][0])]
+    rc = lib().zkgpu_test_records_rlc(vk_path.encode(), ptr, ctypes.c_size_t(n), _weights(weights, n), gt, sums.ctypes.data_as(ctypes.c_void_p))
+    if rc < 0: _check(rc)
+    return rc == 1, bytes(gt), _ints448(sums[:7 * (ni + 1)])
+def rlc_sums_host(inputs, weights, flags):
+    """zkgpu_test_rlc_sums_host: inputs (n, n_inputs, 4) uint64 canonical, weights n ints, flags n bytes -> the host loop's integers [sum r_i, sum r_i x_i0, ...] over flag 1"""
+    inputs = np.ascontiguousarray(inputs, dtype=np.uint64); n = len(weights); ni = inputs.shape[1] if n else 0; fl = np.ascontiguousarray(flags, dtype=np.uint8); assert fl.shape == (n,)
+    sums = np.zeros(7 * (ni + 1), dtype=np.uint64)
+    _check(lib().zkgpu_test_rlc_sums_host(_bytes(inputs) if inputs.size else None, ctypes.c_size_t(ni), _weights(weights, n) or b"\0", _bytes(fl) if n else b"\0", ctypes.c_size_t(n), sums.ctypes.data_as(ctypes.c_void_p)))
+    return _ints448(sums)
+
 def verify_schedule_on_host(vk_path, proof_hex, inputs):
     """the GPU verifier's operation schedule (csrc/verify_sched.hpp) interpreted on the host: (accept, {rounds, slots, products, linear_ops, constants, mul_waves, lin8_waves, lin1_waves}); needs no device"""
     buf = b"".join(int(x).to_bytes(32, "little") for x in inputs); st = (ctypes.c_uint32 * 8)()
@@ -327,6 +371,10 @@ class Zk:
             arr[i].kind = KIND[kind] if isinstance(kind, str) else int(kind); pb = proof.encode() if isinstance(proof, str) else proof; keep.append(pb); arr[i].proof = pb; arr[i].value_s = int(value_s or 0)
             for j, a in enumerate(args): hb = self.hx(a); keep.append(hb); arr[i].args[j] = hb
         ok = (ctypes.c_ubyte * max(1, len(items)))(); self.L.verifyBlock.restype = ctypes.c_int; rc = self.L.verifyBlock(arr, len(items), ok); return rc, [bool(ok[i]) for i in range(len(items))]
+    def VerifyBlockRecords(self, items):
+        """include/zk_records.h: the items of VerifyBlock (or an array records_from_items made of them) as one array of binary records -> (accepted, [bool])"""
+        recs = items if isinstance(items, np.ndarray) else records_from_items(items); recs, ptr, n = _recs(recs)
+        ok = (ctypes.c_ubyte * max(1, n))(); self.L.verifyBlockRecords.restype = ctypes.c_int; rc = self.L.verifyBlockRecords(ptr, n, ok); return rc, [bool(ok[i]) for i in range(n)]
     def GenRedeemProof(self, value, value_old, sn_old, r_old, sn, r, cmtA_old, cmtA, value_s, sk):
         return self.L.genRedeemproof(ctypes.c_uint64(value), ctypes.c_uint64(value_old), self.hx(sn_old), self.hx(r_old), self.hx(sn), self.hx(r), self.hx(cmtA_old), self.hx(cmtA), ctypes.c_uint64(value_s), self.hx(sk)).decode()
     def VerifyRedeemProof(self, proof, cmtA_old, sn_old, cmtA, value_s): return bool(self.L.verifyRedeemproof(proof.encode(), self.hx(cmtA_old), self.hx(sn_old), self.hx(cmtA), ctypes.c_uint64(value_s)))

@@ -22,6 +22,7 @@
 #define ZKGPU_H
 #include <stddef.h>
 #include <stdint.h>
+#include "zk_records.h"
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -180,6 +181,19 @@ int zkgpu_test_verify_rlc_device(const char *vk_path, const char *proofs_hex, co
 /* process-wide: out[0] = block equations that held, out[1] = equations that failed, out[2] = calls (zkgpu_verify_batch_rlc, verifyBlock) in which no record was
  * decided by an equation */
 int zkgpu_verify_rlc_counters(uint64_t out[3]);
+/* zkgpu_verify_batch_rlc for records of ONE kind as zk_records.h lays them out (a record of another kind than the first is an argument error): the proofs are
+ * parsed and the statements packed on the device (k_ingest_records), by the records' kind; a key whose input count is not the kind's rejects the whole call
+ * (strong IC).  weights, ok, by_equation as there. */
+int zkgpu_verify_records_rlc(const char *vk_path, const zk_block_record *recs, size_t n, const uint8_t *weights, uint8_t *ok, uint32_t *by_equation);
+/* test entries.  zkgpu_test_ingest_records: what the ingest makes of n records of one kind — items_out: n x 256 bytes (A.x A.y | B.x.c0 B.x.c1 B.y.c0 B.y.c1 | C.x C.y,
+ * Montgomery; all zero where the 512 characters are not a proof), inputs_out: n x *n_inputs_out canonical field elements (room for 6 a record), parsed_out: n bytes —
+ * from the kernel (device = 1) or from the host converter built on proof_from_hex and pack_public_bits (device = 0: needs no device).
+ * zkgpu_test_records_rlc: the equation through the device path from records, whatever their count: returns 1 / 0 as zkgpu_test_verify_rlc_device; gt_out: 384 bytes;
+ * sums_out: (n_inputs + 1) x 7 words, the device's integers sum r_i and sum r_i x_ij over the records in the equation.
+ * zkgpu_test_rlc_sums_host: the same integers by the host loop, for given inputs (n x n_inputs canonical elements), weights and flags (1 = in the equation). */
+int zkgpu_test_ingest_records(const zk_block_record *recs, size_t n, int device, uint8_t *items_out, uint8_t *inputs_out, size_t *n_inputs_out, uint8_t *parsed_out);
+int zkgpu_test_records_rlc(const char *vk_path, const zk_block_record *recs, size_t n, const uint8_t *weights, uint8_t *gt_out, uint64_t *sums_out);
+int zkgpu_test_rlc_sums_host(const uint8_t *inputs, size_t n_inputs, const uint8_t *weights, const uint8_t *flags, size_t n, uint64_t *sums_out);
 
 /* ---- the commitment tree resident in HBM (DESIGN.md "Commitment tree"; the drop-in level is zk_tree.h) -------------------------------------------------
  * An append-only SHA-256 Merkle tree of depth 1..32: node = one compression of left || right from the standard IV without padding, unseen leaves all zero
