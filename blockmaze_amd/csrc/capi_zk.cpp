@@ -30,6 +30,7 @@
 #include "../../include/zk_block.h"
 #include "../../include/zk_records.h"
 #include "../../include/zk_tree.h"
+#include "../../include/zk_roots.h"
 #include "../../include/zkgpu.h"
 #include "blockmaze_circuits.hpp"
 #include "groth16.hpp"
@@ -1423,6 +1424,82 @@ char *genDepositproofTree(uint64_t value, uint64_t value_old, char *sn_old, char
 bool verifyDepositproofDepth(int depth, char *data, char *RT, char *pk, char *cmtb_old, char *snold, char *cmtb, char *sns) {
   if (depth < 1 || depth > 32) return false;
   const char *a[6] = {RT, pk, cmtb_old, snold, cmtb, sns}; return verify(CircuitKind::Deposit, data, public_bits(CircuitKind::Deposit, a, 0), (size_t)depth); }
+
+// ---- the roots of many commitment lists (DESIGN.md "Roots of many lists"; include/zkgpu.h, include/zk_roots.h) --------------------------------------------------
+// The device road is gpu_list_roots.hip; list_roots_host is the same roots from merkle_root, list by list — the model the kernel is tested against and the road of
+// verifyBlockRecordsRoots without a device or after a device failure, as records_to_host is for the records.
+static_assert(sizeof(zkgpu_leaf_range) == sizeof(LeafRange) && sizeof(zk_cmt_range) == sizeof(LeafRange), "a leaf range is two 64-bit words at every level");
+static int list_roots_args(int depth, const uint8_t *leaves, size_t n_leaves, const zkgpu_leaf_range *lists, size_t n_lists, const uint8_t *roots) {
+  if (depth < 1 || depth > 32) { zkgpu_set_error("list roots: the depth must lie between 1 and 32"); return ZKGPU_ERR_ARG; }
+  if ((n_leaves && !leaves) || (n_lists && (!lists || !roots))) { zkgpu_set_error("list roots: a null pointer"); return ZKGPU_ERR_ARG; }
+  for (size_t i = 0; i < n_lists; i++) {
+    if (lists[i].first > n_leaves || lists[i].count > n_leaves - lists[i].first) { zkgpu_set_error("list roots: list " + std::to_string(i) + " leaves the array"); return ZKGPU_ERR_ARG; }
+    if (lists[i].count > (1ull << depth)) { zkgpu_set_error("list roots: list " + std::to_string(i) + " holds more than 2^" + std::to_string(depth) + " leaves"); return ZKGPU_ERR_ARG; }
+  }
+  return ZKGPU_OK;
+}
+static void list_roots_host(int depth, const uint8_t *leaves, const zkgpu_leaf_range *lists, size_t n_lists, bool hash_order, uint8_t *roots) {
+  std::vector<Blob256> lv;
+  for (size_t i = 0; i < n_lists; i++) {
+    lv.resize((size_t)lists[i].count);
+    for (size_t k = 0; k < lv.size(); k++) { const uint8_t *src = leaves + 32 * ((size_t)lists[i].first + k);
+      if (hash_order) for (int b = 0; b < 32; b++) lv[k].b[b] = src[31 - b]; else memcpy(lv[k].b, src, 32); }
+    const Blob256 r = merkle_root(lv, (size_t)depth);
+    if (hash_order) for (int b = 0; b < 32; b++) roots[32 * i + b] = r.b[31 - b]; else memcpy(roots + 32 * i, r.b, 32);
+  }
+}
+int zkgpu_list_roots(int depth, const uint8_t *leaves, size_t n_leaves, const zkgpu_leaf_range *lists, size_t n_lists, int hash_order, uint8_t *roots) {
+  const int rc = guarded_host([&] { return list_roots_args(depth, leaves, n_leaves, lists, n_lists, roots); }); if (rc != ZKGPU_OK) return rc;
+  return guarded([&] { list_roots_dev(depth, leaves, n_leaves, (const LeafRange *)lists, n_lists, hash_order != 0, roots); return ZKGPU_OK; }); }
+int zkgpu_test_list_roots_host(int depth, const uint8_t *leaves, size_t n_leaves, const zkgpu_leaf_range *lists, size_t n_lists, int hash_order, uint8_t *roots) { return guarded_host([&] {
+  const int rc = list_roots_args(depth, leaves, n_leaves, lists, n_lists, roots); if (rc != ZKGPU_OK) return rc;
+  list_roots_host(depth, leaves, lists, n_lists, hash_order != 0, roots); return ZKGPU_OK; }); }
+int zkgpu_test_list_roots_launches(uint64_t *launches) { if (!launches) return ZKGPU_ERR_ARG; *launches = list_roots_launches(); return ZKGPU_OK; }
+
+int genRoots(const zk_cmt_lists *l, int depth, uint8_t *roots) {
+  if (!l || l->n_lists < 0) { zkgpu_set_error("genRoots: no lists"); return -1; }
+  const int rc = zkgpu_list_roots(depth, l->cmts, (size_t)l->n_cmts, (const zkgpu_leaf_range *)l->lists, (size_t)l->n_lists, 1, roots);
+  if (rc != ZKGPU_OK) { fprintf(stderr, "libzkgpu: genRoots: %s\n", zkgpu_last_error()); return -1; }
+  return 0;
+}
+// verifyBlockRecords, then RT of every record that names a list against that list's depth-8 root.  The roots of all lists are made once, on the device; a list of
+// more than 256 commitments has no depth-8 root: it is computed as an empty one and rejects whoever names it.
+int verifyBlockRecordsRoots(const zk_block_record *recs, int n, const zk_cmt_lists *l, const int32_t *list_of, unsigned char *ok) {
+  if (n < 0 || (n && (!recs || !ok))) return -1;
+  auto fail = [&](const std::string &why) { zkgpu_set_error(why); fprintf(stderr, "libzkgpu: verifyBlockRecordsRoots: %s\n", why.c_str()); for (int i = 0; i < n; i++) ok[i] = 0; return -1; };
+  try {
+    bool any = false; if (list_of) for (int i = 0; i < n; i++) any |= list_of[i] >= 0;
+    if (any && !l) return fail("records name lists and there are none");
+    size_t n_lists = 0; std::vector<uint8_t> roots, usable; std::vector<zkgpu_leaf_range> ranges;
+    if (l) {
+      if (l->n_lists < 0 || (l->n_lists && !l->lists) || (l->n_cmts && !l->cmts)) return fail("a null pointer in the lists");
+      n_lists = (size_t)l->n_lists; usable.assign(n_lists, 0); ranges.assign(n_lists, zkgpu_leaf_range{0, 0});
+      { HostSpan span("host.roots_ranges");
+        for (size_t j = 0; j < n_lists; j++) {
+          const zk_cmt_range &r = l->lists[j]; if (r.first > l->n_cmts || r.count > l->n_cmts - r.first) return fail("list " + std::to_string(j) + " leaves the array of commitments");
+          if (r.count <= 256) { usable[j] = 1; ranges[j] = zkgpu_leaf_range{r.first, r.count}; }
+        } }
+      if (any) {
+        roots.resize(32 * n_lists); bool done = false;
+        if (gpu_available()) {
+          try { std::lock_guard<std::mutex> gl(g_gpu_mutex); list_roots_dev(8, l->cmts, (size_t)l->n_cmts, (const LeafRange *)ranges.data(), n_lists, true, roots.data()); done = true; }
+          catch (const std::exception &e) { fprintf(stderr, "libzkgpu: verifyBlockRecordsRoots: the roots failed on the device (%s); computing %zu root(s) on the host\n", e.what(), n_lists); }
+        }
+        if (!done) list_roots_host(8, l->cmts, ranges.data(), n_lists, true, roots.data());
+      }
+    }
+    const int rc = verify_block_records(recs, n, ok, "verifyBlockRecordsRoots"); if (rc < 0 || !list_of) return rc;
+    HostSpan span("host.roots_compare"); int accepted = 0;
+    for (int i = 0; i < n; i++) {
+      const int32_t j = list_of[i];
+      if (ok[i] && j != -1 && (j < 0 || (size_t)j >= n_lists || !usable[j] || recs[i].kind != ZK_KIND_DEPOSIT || memcmp(recs[i].args[0], &roots[32 * (size_t)j], 32))) ok[i] = 0;
+      accepted += ok[i];
+    }
+    return accepted;
+  }
+  catch (const std::exception &e) { return fail(e.what()); }
+  catch (...) { return fail("unknown error"); }
+}
 
 // the reference's symbol names, exported by libzkgpu.so itself (the four libzk_*.so forward to the zkgpu_abi_* names above)
 char *genCMT(uint64_t v, char *a, char *b) { return zkgpu_abi_genCMT(v, a, b); }

@@ -188,6 +188,14 @@ class CommitmentTree {
   struct Impl; std::unique_ptr<Impl> impl;
 };
 
+// The roots of many independent commitment lists (gpu_list_roots.hip): list i = leaves[first .. first + count) of one shared array, roots[i] = the root of the tree
+// above over that list alone (notes.cpp: merkle_root), in the caller's order.  hash_order: leaves and roots as the bytes of the common.Hash instead of blob order.
+// The caller has checked the arguments (depth 1..32, every range inside the array, count <= 2^depth) and holds the device mutex; runs on the main stream and
+// returns after it has been synchronised.  One process-wide workspace, kept and grown.
+struct LeafRange { uint64_t first, count; };
+void list_roots_dev(int depth, const uint8_t *leaves, size_t n_leaves, const LeafRange *lists, size_t n_lists, bool hash_order, uint8_t *roots);
+uint64_t list_roots_launches();   // root kernels launched so far, process-wide (tests: the count does not grow with the number of lists)
+
 // Evaluation domain of size m = 2^k or 2^k + 2^r (libfqfft get_evaluation_domain, get_evaluation_domain.tcc:33-52) with
 // its twiddle / coset tables resident in HBM.
 struct R1csHost;

@@ -329,6 +329,33 @@ def tree_host(depth, leaves, index=None, want_root=True):
     _check(lib().zkgpu_test_tree_host(int(depth), bytes(buf) if n else None, ctypes.c_size_t(n), ctypes.c_uint64(index or 0), root, path))
     return (root.raw if want_root else None), ([path.raw[32 * k:32 * k + 32] for k in range(depth)] if path is not None else None)
 
+# ---- the roots of many commitment lists (include/zkgpu.h "the roots of many commitment lists"; the drop-in level is include/zk_roots.h) ----
+def _leaf_array(leaves):
+    """leaves: an (n, 32) uint8 array, one bytes object of n x 32 bytes, or a list of 32-byte strings -> flat uint8 array"""
+    if isinstance(leaves, np.ndarray): a = np.ascontiguousarray(leaves, dtype=np.uint8).reshape(-1)
+    else: a = np.frombuffer(leaves if isinstance(leaves, (bytes, bytearray)) else b"".join(bytes(x) for x in leaves), dtype=np.uint8)
+    assert a.size % 32 == 0; return a
+def _leaf_ranges(lists):
+    r = np.ascontiguousarray(np.asarray(lists, dtype=np.uint64).reshape(-1, 2)); return r, (r.ctypes.data_as(ctypes.c_void_p) if r.shape[0] else None), int(r.shape[0])
+def _list_roots(fn, depth, leaves, lists, hash_order):
+    buf = _leaf_array(leaves); r, ptr, n = _leaf_ranges(lists); out = np.zeros((max(1, n), 32), dtype=np.uint8)
+    _check(fn(int(depth), _bytes(buf) if buf.size else None, ctypes.c_size_t(buf.size // 32), ptr, ctypes.c_size_t(n), int(bool(hash_order)), _bytes(out))); return out[:n]
+def list_roots(depth, leaves, lists, hash_order=False):
+    """zkgpu_list_roots: lists = [(first, count)] into the shared leaves -> (n_lists, 32) uint8, root i over leaves[first:first + count] alone, on the device.
+    hash_order: leaves and roots as the bytes of the common.Hash instead of blob order"""
+    return _list_roots(lib().zkgpu_list_roots, depth, leaves, lists, hash_order)
+def list_roots_host(depth, leaves, lists, hash_order=False):
+    """zkgpu_test_list_roots_host: the same roots by the host model (notes.cpp: merkle_root), no device needed"""
+    return _list_roots(lib().zkgpu_test_list_roots_host, depth, leaves, lists, hash_order)
+def list_roots_launches():
+    """root kernels launched by this process so far"""
+    k = ctypes.c_uint64(0); _check(lib().zkgpu_test_list_roots_launches(ctypes.byref(k))); return int(k.value)
+class _CmtLists(ctypes.Structure):   # zk_cmt_lists
+    _fields_ = [("cmts", ctypes.c_void_p), ("n_cmts", ctypes.c_uint64), ("lists", ctypes.c_void_p), ("n_lists", ctypes.c_int)]
+def _cmt_lists(cmts, lists):
+    buf = _leaf_array(cmts); r, ptr, n = _leaf_ranges(lists)
+    return _CmtLists(buf.ctypes.data_as(ctypes.c_void_p) if buf.size else None, buf.size // 32, ptr, n), (buf, r)   # (the arrays must outlive the call)
+
 class Zk:
     """the drop-in symbols (what go-ethereum/zktx calls through cgo), bound the way zktx.go marshals them: "0x…" hex strings and uint64"""
     def __init__(self):
@@ -375,6 +402,18 @@ class Zk:
         """include/zk_records.h: the items of VerifyBlock (or an array records_from_items made of them) as one array of binary records -> (accepted, [bool])"""
         recs = items if isinstance(items, np.ndarray) else records_from_items(items); recs, ptr, n = _recs(recs)
         ok = (ctypes.c_ubyte * max(1, n))(); self.L.verifyBlockRecords.restype = ctypes.c_int; rc = self.L.verifyBlockRecords(ptr, n, ok); return rc, [bool(ok[i]) for i in range(n)]
+    def GenRoots(self, cmts, lists, depth=8):
+        """include/zk_roots.h: cmts = the shared array of commitments (big-endian, as common.Hash), lists = [(first, count)] -> [root as big-endian bytes]; raises on -1"""
+        l, keep = _cmt_lists(cmts, lists); out = np.zeros((max(1, l.n_lists), 32), dtype=np.uint8); self.L.genRoots.restype = ctypes.c_int
+        if self.L.genRoots(ctypes.byref(l), int(depth), _bytes(out)) != 0: raise ZkGpuError("genRoots: " + lib().zkgpu_last_error().decode())
+        return [out[i].tobytes() for i in range(l.n_lists)]
+    def VerifyBlockRecordsRoots(self, items, cmts, lists, list_of):
+        """include/zk_roots.h: VerifyBlockRecords, and RT of record i against the depth-8 root of list list_of[i] (-1: no root check) -> (accepted, [bool]).
+        lists = None passes no zk_cmt_lists at all"""
+        recs = items if isinstance(items, np.ndarray) else records_from_items(items); recs, ptr, n = _recs(recs)
+        l, keep = _cmt_lists(cmts, lists) if lists is not None else (None, None); lo = np.ascontiguousarray(list_of, dtype=np.int32); assert lo.shape == (n,)
+        ok = (ctypes.c_ubyte * max(1, n))(); self.L.verifyBlockRecordsRoots.restype = ctypes.c_int
+        rc = self.L.verifyBlockRecordsRoots(ptr, n, ctypes.byref(l) if l is not None else None, lo.ctypes.data_as(ctypes.c_void_p) if n else None, ok); return rc, [bool(ok[i]) for i in range(n)]
     def GenRedeemProof(self, value, value_old, sn_old, r_old, sn, r, cmtA_old, cmtA, value_s, sk):
         return self.L.genRedeemproof(ctypes.c_uint64(value), ctypes.c_uint64(value_old), self.hx(sn_old), self.hx(r_old), self.hx(sn), self.hx(r), self.hx(cmtA_old), self.hx(cmtA), ctypes.c_uint64(value_s), self.hx(sk)).decode()
     def VerifyRedeemProof(self, proof, cmtA_old, sn_old, cmtA, value_s): return bool(self.L.verifyRedeemproof(proof.encode(), self.hx(cmtA_old), self.hx(sn_old), self.hx(cmtA), ctypes.c_uint64(value_s)))

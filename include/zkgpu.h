@@ -211,6 +211,18 @@ int zkgpu_test_tree_launches(zkgpu_tree *t, uint64_t *launches);            /* t
 /* test entry, host only: root (if root != NULL) and, if path != NULL, the path of `index` by notes.cpp's tree_levels */
 int zkgpu_test_tree_host(int depth, const uint8_t *leaves, size_t n, uint64_t index, uint8_t root[32], uint8_t *path);
 
+/* ---- the roots of many commitment lists in one call (DESIGN.md "Roots of many lists"; the drop-in level is zk_roots.h) ------------------------------------
+ * List i is leaves[first .. first + count) of one shared array of 32-byte leaves; ranges may overlap, coincide or be empty.  roots[i] is the root of the tree
+ * above (depth 1..32) over that list alone, an empty list giving the empty root of the depth.  hash_order = 0: leaves and roots in blob order, as the tree entries
+ * above; 1: both as the bytes of the common.Hash (zk_records.h), the blob reversed.  ZKGPU_ERR_ARG, with nothing written, for a depth outside 1..32, a range that
+ * leaves [0, n_leaves), a count above 2^depth, or a null pointer where a size is not 0.  One upload, a number of kernel launches that depends on the sizes present
+ * and not on the number of lists, one download. */
+typedef struct { uint64_t first, count; } zkgpu_leaf_range;
+int zkgpu_list_roots(int depth, const uint8_t *leaves, size_t n_leaves, const zkgpu_leaf_range *lists, size_t n_lists, int hash_order, uint8_t *roots);
+/* test entries: the same roots by notes.cpp's merkle_root, list by list (needs no device); the process-wide number of root-kernel launches so far */
+int zkgpu_test_list_roots_host(int depth, const uint8_t *leaves, size_t n_leaves, const zkgpu_leaf_range *lists, size_t n_lists, int hash_order, uint8_t *roots);
+int zkgpu_test_list_roots_launches(uint64_t *launches);
+
 #ifdef __cplusplus
 }
 #endif
