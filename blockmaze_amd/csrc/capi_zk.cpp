@@ -30,6 +30,7 @@
 #include "../../include/zk_block.h"
 #include "../../include/zk_records.h"
 #include "../../include/zk_tree.h"
+#include "../../include/zk_tree_states.h"
 #include "../../include/zk_roots.h"
 #include "../../include/zkgpu.h"
 #include "blockmaze_circuits.hpp"
@@ -1372,6 +1373,24 @@ int zkgpu_tree_find(zkgpu_tree *t, const uint8_t leaf[32], uint64_t *index) { re
   if (!t->t.find(leaf, *index)) { zkgpu_set_error("commitment tree: the leaf is not in the tree"); return ZKGPU_ERR_ARG; }
   return ZKGPU_OK; }); }
 int zkgpu_test_tree_launches(zkgpu_tree *t, uint64_t *launches) { return guarded_tree(t, [&] { if (!launches) return ZKGPU_ERR_ARG; *launches = t->t.launches(); return ZKGPU_OK; }); }
+// past states (DESIGN.md "Past states of the commitment tree"): the tree checks sizes and indices under its own lock, before anything is queued
+int zkgpu_tree_roots_at(zkgpu_tree *t, const uint64_t *sizes, size_t q, uint8_t *roots) { return guarded_tree(t, [&] {
+  if (q && (!sizes || !roots)) { zkgpu_set_error("commitment tree: a null pointer"); return ZKGPU_ERR_ARG; }
+  if (!t->t.roots_at(sizes, q, roots)) { zkgpu_set_error("commitment tree: a size above the tree's size"); return ZKGPU_ERR_ARG; }
+  return ZKGPU_OK; }); }
+int zkgpu_tree_paths_at(zkgpu_tree *t, uint64_t size, const uint64_t *indices, size_t q, uint8_t *siblings, uint8_t root[32]) { return guarded_tree(t, [&] {
+  if (q && (!indices || !siblings)) { zkgpu_set_error("commitment tree: a null pointer"); return ZKGPU_ERR_ARG; }
+  if (!t->t.paths_at(size, indices, q, siblings, root)) { zkgpu_set_error("commitment tree: size " + std::to_string(size) + " is above the tree's size, or an index is not below it"); return ZKGPU_ERR_ARG; }
+  return ZKGPU_OK; }); }
+int zkgpu_tree_find_at(zkgpu_tree *t, uint64_t size, const uint8_t leaf[32], uint64_t *index) { return guarded_tree(t, [&] {
+  if (!leaf || !index) return ZKGPU_ERR_ARG;
+  uint64_t got = 0;
+  if (!t->t.find_at(size, leaf, got)) { zkgpu_set_error("commitment tree: the leaf is not among the first " + std::to_string(size) + " leaves, or the tree is smaller"); return ZKGPU_ERR_ARG; }
+  *index = got; return ZKGPU_OK; }); }
+int zkgpu_tree_rewind(zkgpu_tree *t, uint64_t size) { return guarded_tree(t, [&] {
+  if (!t->t.rewind(size)) { zkgpu_set_error("commitment tree: cannot rewind to " + std::to_string(size) + " leaves, the tree holds fewer"); return ZKGPU_ERR_ARG; }
+  return ZKGPU_OK; }); }
+int zkgpu_test_tree_state_launches(zkgpu_tree *t, uint64_t *launches) { return guarded_tree(t, [&] { if (!launches) return ZKGPU_ERR_ARG; *launches = t->t.state_launches(); return ZKGPU_OK; }); }
 int zkgpu_test_tree_host(int depth, const uint8_t *leaves, size_t n, uint64_t index, uint8_t root[32], uint8_t *path) { return guarded_host([&] {
   if (depth < 1 || depth > 32 || (n && !leaves) || n > (1ull << depth) || (path && index >= n)) return ZKGPU_ERR_ARG;
   std::vector<Blob256> lv(n); if (n) memcpy(lv.data(), leaves, 32 * n);
@@ -1397,9 +1416,10 @@ char *zkTreeRoot(zk_tree *t) {
   Blob256 r; if (guarded_tree(t, [&] { t->t.root(r.b); return ZKGPU_OK; }) != ZKGPU_OK) { fprintf(stderr, "libzkgpu: zkTreeRoot: %s\n", zkgpu_last_error()); return nullptr; }
   return hash_out(r);
 }
-// genDepositproof against the resident tree: ONE snapshot gives the leaf's index, its path and the root they belong to; the proof's statement is that root
-char *genDepositproofTree(uint64_t value, uint64_t value_old, char *sn_old, char *r_old, char *sn, char *r, char *sns, char *rs, char *cmtB_old, char *cmtB,
-    uint64_t value_s, char *pk, char *sn_A_old, char *cmtS, char *sk, zk_tree *t, char rt_out[65]) {
+// genDepositproof against the resident tree: ONE snapshot gives the leaf's index, its path and the root they belong to; the proof's statement is that root.
+// size < 0: the tree's newest state (genDepositproofTree); otherwise the state of the first `size` leaves (genDepositproofTreeAt)
+static char *deposit_proof_tree(uint64_t value, uint64_t value_old, char *sn_old, char *r_old, char *sn, char *r, char *sns, char *rs, char *cmtB_old, char *cmtB,
+    uint64_t value_s, char *pk, char *sn_A_old, char *cmtS, char *sk, zk_tree *t, bool at, long long size, char rt_out[65]) {
   if (rt_out) rt_out[0] = 0;
   try {
     const std::string sentinel = proof_to_hex(default_proof());
@@ -1411,7 +1431,9 @@ char *genDepositproofTree(uint64_t value, uint64_t value_old, char *sn_old, char
     DepositInputs in = deposit_fields(value, value_old, sn_old, r_old, sn, r, sns, rs, cmtB_old, cmtB, value_s, pk, sn_A_old, cmtS, sk);
     CommitmentTree::Snapshot snap;
     // the reference throws out of IncrementalMerkleTree::path() here (IncrementalMerkleTree.tcc:214-216)
-    if (!t->t.snapshot(in.cmtS.b, snap)) throw std::runtime_error("cmtS is not among the commitments of the tree");
+    if (at && size < 0) throw std::runtime_error("genDepositproofTreeAt: a negative size");
+    if (at ? !t->t.snapshot_at((uint64_t)size, in.cmtS.b, snap) : !t->t.snapshot(in.cmtS.b, snap))
+      throw std::runtime_error(at ? "cmtS is not among the first " + std::to_string(size) + " commitments of the tree, or the tree holds fewer" : std::string("cmtS is not among the commitments of the tree"));
     const size_t depth = (size_t)t->t.depth(); in.path.resize(depth); memcpy(in.path.data(), snap.path.data(), 32 * depth); in.index_bits = snap.index_bits; memcpy(in.rt.b, snap.root, 32);
     char *proof = generate(CircuitKind::Deposit, [&](Circuit &c) { assign_deposit(c, in); }, depth);
     if (proof && sentinel != proof) { const std::string rt = blob_to_hex(in.rt.b, 32); memcpy(rt_out, rt.c_str(), 65); }
@@ -1420,6 +1442,40 @@ char *genDepositproofTree(uint64_t value, uint64_t value_old, char *sn_old, char
   catch (const std::exception &e) { zkgpu_set_error(e.what()); fprintf(stderr, "libzkgpu: %s\n", e.what()); }
   catch (...) { zkgpu_set_error("unknown error"); }
   try { return dup_string(proof_to_hex(default_proof())); } catch (...) { return nullptr; }
+}
+char *genDepositproofTree(uint64_t value, uint64_t value_old, char *sn_old, char *r_old, char *sn, char *r, char *sns, char *rs, char *cmtB_old, char *cmtB,
+    uint64_t value_s, char *pk, char *sn_A_old, char *cmtS, char *sk, zk_tree *t, char rt_out[65]) {
+  return deposit_proof_tree(value, value_old, sn_old, r_old, sn, r, sns, rs, cmtB_old, cmtB, value_s, pk, sn_A_old, cmtS, sk, t, false, 0, rt_out); }
+// ---- include/zk_tree_states.h: roots and proofs at past sizes, rewind ----
+char *genDepositproofTreeAt(uint64_t value, uint64_t value_old, char *sn_old, char *r_old, char *sn, char *r, char *sns, char *rs, char *cmtB_old, char *cmtB,
+    uint64_t value_s, char *pk, char *sn_A_old, char *cmtS, char *sk, zk_tree *t, long long size, char rt_out[65]) {
+  return deposit_proof_tree(value, value_old, sn_old, r_old, sn, r, sns, rs, cmtB_old, cmtB, value_s, pk, sn_A_old, cmtS, sk, t, true, size, rt_out); }
+int zkTreeRootsAt(zk_tree *t, const long long *sizes, int q, uint8_t *roots) {
+  const int rc = guarded_tree(t, [&] {
+    if (q < 0 || (q && (!sizes || !roots))) { zkgpu_set_error("zkTreeRootsAt: a negative count or a null pointer"); return ZKGPU_ERR_ARG; }
+    std::vector<uint64_t> m((size_t)q); std::vector<uint8_t> out(32 * (size_t)q);
+    for (int i = 0; i < q; i++) { if (sizes[i] < 0) { zkgpu_set_error("zkTreeRootsAt: a negative size"); return ZKGPU_ERR_ARG; } m[i] = (uint64_t)sizes[i]; }
+    if (!t->t.roots_at(m.data(), (size_t)q, out.data())) { zkgpu_set_error("zkTreeRootsAt: a size above the tree's size"); return ZKGPU_ERR_ARG; }
+    for (size_t i = 0; i < (size_t)q; i++) for (int b = 0; b < 32; b++) roots[32 * i + b] = out[32 * i + 31 - b];   // blob order -> the bytes of the common.Hash
+    return ZKGPU_OK; });
+  if (rc != ZKGPU_OK) { fprintf(stderr, "libzkgpu: zkTreeRootsAt: %s\n", zkgpu_last_error()); return -1; }
+  return 0;
+}
+char *zkTreeRootAt(zk_tree *t, long long size) {
+  Blob256 r;
+  const int rc = guarded_tree(t, [&] {
+    const uint64_t m = (uint64_t)size;
+    if (size < 0 || !t->t.roots_at(&m, 1, r.b)) { zkgpu_set_error("zkTreeRootAt: the tree does not hold " + std::to_string(size) + " leaves"); return ZKGPU_ERR_ARG; }
+    return ZKGPU_OK; });
+  if (rc != ZKGPU_OK) { fprintf(stderr, "libzkgpu: zkTreeRootAt: %s\n", zkgpu_last_error()); return nullptr; }
+  return hash_out(r);
+}
+long long zkTreeRewind(zk_tree *t, long long size) {
+  const int rc = guarded_tree(t, [&] {
+    if (size < 0 || !t->t.rewind((uint64_t)size)) { zkgpu_set_error("zkTreeRewind: the tree does not hold " + std::to_string(size) + " leaves"); return ZKGPU_ERR_ARG; }
+    return ZKGPU_OK; });
+  if (rc != ZKGPU_OK) { fprintf(stderr, "libzkgpu: zkTreeRewind: %s\n", zkgpu_last_error()); return -1; }
+  return size;
 }
 bool verifyDepositproofDepth(int depth, char *data, char *RT, char *pk, char *cmtb_old, char *snold, char *cmtb, char *sns) {
   if (depth < 1 || depth > 32) return false;

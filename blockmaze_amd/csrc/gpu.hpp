@@ -170,8 +170,8 @@ size_t block_scalar_sums_scratch(size_t n_inputs);
 void block_scalar_sums_dev(const Fe32 *inputs, size_t n_inputs, const uint8_t *weights, const uint8_t *flags, size_t n, uint64_t *partials, uint64_t *out);
 
 // The commitment tree of the deposit circuit, resident in HBM (gpu_tree.hip): an append-only SHA-256 Merkle tree of depth 1..32 with all-zero unseen leaves,
-// the tree of notes.cpp:tree_levels.  Leaves, siblings and roots are 32-byte blobs in blob byte order.  One mutex per tree: append, root, path, find and snapshot
-// are each atomic with respect to the others, and each runs on the main stream under the device mutex.
+// the tree of notes.cpp:tree_levels.  Leaves, siblings and roots are 32-byte blobs in blob byte order.  One mutex per tree: append, root, path, find, snapshot and the
+// past-state entries are each atomic with respect to the others, and each runs on the main stream under the device mutex.
 class CommitmentTree {
  public:
   // one state of the tree seen under one lock: a proof must never pair the path of one state with the root of another
@@ -185,6 +185,15 @@ class CommitmentTree {
   bool find(const uint8_t leaf[32], uint64_t &index);                // the first leaf equal to the blob; false: none
   bool snapshot(const uint8_t leaf[32], Snapshot &out);              // false: the leaf is not in the tree (size and root are filled all the same)
   uint64_t launches() const;                                         // append kernels launched so far (tests: a small append is one launch)
+  // Past states (DESIGN.md "Past states of the commitment tree"): state m = the tree of the first m leaves, 0 <= m <= size().  Each entry checks its arguments
+  // before anything is queued — false: a size above size(), an index not below its size, a null pointer; nothing is written and nothing changes then — and is at
+  // most two kernel launches and one download whatever q is.
+  bool roots_at(const uint64_t *sizes, size_t q, uint8_t *out /* q x 32 */);                       // one launch; sizes may repeat and come in any order
+  bool paths_at(uint64_t size, const uint64_t *indices, size_t q, uint8_t *siblings /* q x depth x 32 */, uint8_t *root /* 32, or null */);
+  bool find_at(uint64_t size, const uint8_t leaf[32], uint64_t &index);                           // the first of the first `size` leaves equal to the blob
+  bool snapshot_at(uint64_t size, const uint8_t leaf[32], Snapshot &out);                          // snapshot() of state `size`; false also if the tree is smaller
+  bool rewind(uint64_t size);                                        // the tree becomes state `size`: the leaves from `size` on are gone (a reorganisation)
+  uint64_t state_launches() const;                                   // kernels launched by the five entries above (tests)
   struct Impl; std::unique_ptr<Impl> impl;
 };
 

@@ -86,9 +86,89 @@ __global__ void __launch_bounds__(64) k_tree_path(TreeGeom G, uint64_t n, uint64
   ((uint4 *)(out + 32 * (k + 1)))[0] = ((const uint4 *)src)[0]; ((uint4 *)(out + 32 * (k + 1)))[1] = ((const uint4 *)src)[1];
 }
 
+// ---- past states (DESIGN.md "Past states of the commitment tree") ---------------------------------------------------------------------------------------------
+// State m, 1 <= m <= n, is the tree of the first m leaves.  It differs from the stored nodes only along its right edge, one node a level: B_k = node (m - 1) >> k of
+// level k.  Where 2^k divides m that node is complete and stored, so the walk starts at k0 = min(ctz(m), depth) with the stored node; above it
+//   B_k = compress(stored[k-1][j - 1], B_{k-1})  if j = (m - 1) >> (k - 1) is odd (the left sibling is a complete subtree: stored, and the same in every later state)
+//       = compress(B_{k-1}, empty[k-1])           otherwise.
+// One load a level — the sibling or the empty root, fetched before the compression of the level below runs — then the operands are selected and tree_compress is
+// called ONCE: a wave whose lanes differ in parity runs one compression a level, and a kernel holds one copy of it.  sink(k, B_k) sees every level from k0 to depth.
+__device__ __forceinline__ const uint8_t *tree_edge_operand(const TreeGeom &G, uint64_t m, uint32_t k) {   // the other operand of B_k's compression
+  const uint64_t j = (m - 1) >> (k - 1);
+  return (j & 1) ? G.nodes + 32 * (tree_off(G.cap_log, k - 1) + j - 1) : G.empty + 32 * (k - 1);
+}
+// Where m is the same for the whole launch (k_tree_paths_at, k_tree_rewind) the compiler would run the walk on the scalar ALU, which has no rotate: measured 7.5 us a
+// level against 4 on the vector ALU.  The empty statement below holds the node in vector registers, and the compression follows it there.
+__device__ __forceinline__ void tree_in_vgprs(Node &v) {
+#pragma unroll
+  for (int i = 0; i < 8; i++) asm volatile("" : "+v"(v.w[i]));
+}
+template <class Sink> __device__ __forceinline__ Node tree_edge_walk(const TreeGeom &G, uint64_t m, Sink sink) {
+  const uint32_t tz = (uint32_t)__builtin_ctzll(m), k0 = tz < G.depth ? tz : G.depth;
+  Node B = tree_load(G.nodes + 32 * (tree_off(G.cap_log, k0) + ((m - 1) >> k0))); tree_in_vgprs(B); sink(k0, B);
+  if (k0 == G.depth) return B;
+  Node o = tree_load(tree_edge_operand(G, m, k0 + 1));
+#pragma unroll 1
+  for (uint32_t k = k0 + 1; k <= G.depth; k++) {
+    const bool odd = ((m - 1) >> (k - 1)) & 1; Node l, r;
+#pragma unroll
+    for (int i = 0; i < 8; i++) { l.w[i] = odd ? o.w[i] : B.w[i]; r.w[i] = odd ? B.w[i] : o.w[i]; }
+    if (k < G.depth) o = tree_load(tree_edge_operand(G, m, k + 1));
+    B = tree_compress(l, r); sink(k, B);
+  }
+  return B;
+}
+__device__ __forceinline__ void tree_copy32(uint8_t *dst, const uint8_t *src) { ((uint4 *)dst)[0] = ((const uint4 *)src)[0]; ((uint4 *)dst)[1] = ((const uint4 *)src)[1]; }
+
+// out[t] = the root of state sizes[t], one lane a size; size 0 is the empty tree.  The host has checked sizes[t] <= n.
+__global__ void __launch_bounds__(64) k_tree_roots_at(TreeGeom G, const unsigned long long *__restrict__ sizes, uint64_t q, uint8_t *__restrict__ out) {
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; if (t >= q) return;
+  const uint64_t m = sizes[t];
+  if (!m) { tree_copy32(out + 32 * t, G.empty + 32 * G.depth); return; }
+  tree_store(out + 32 * t, tree_edge_walk(G, m, [](uint32_t, const Node &) {}));
+}
+// q leaves of ONE state m >= 1: out = [root of state m | index: 8 bytes, padded to 32 | q x depth siblings, leaf level first].  The indices come from the host
+// (checked: below m) or, for q = 1, from k_tree_find's word (index_dev), which is then written to the index slot; an index that is no leaf of state m leaves the
+// siblings unwritten.  Lane 0 of every workgroup walks the edge into LDS in blob byte order; after the barrier one lane per (leaf, level) gathers: the sibling
+// s = (i >> k) ^ 1 is stored if its subtree is complete in state m, empty if it starts at or beyond m, and otherwise it is the edge node B_k.
+__global__ void __launch_bounds__(256) k_tree_paths_at(TreeGeom G, uint64_t m, const unsigned long long *__restrict__ indices, const unsigned long long *__restrict__ index_dev,
+                                                        uint64_t q, uint8_t *__restrict__ out) {
+  __shared__ uint4 edge[2 * 33];
+  if (threadIdx.x == 0) tree_edge_walk(G, m, [&](uint32_t k, const Node &B) { tree_store((uint8_t *)&edge[2 * k], B); });
+  __syncthreads();
+  const uint8_t *edge_bytes = (const uint8_t *)edge;
+  if (blockIdx.x == 0 && threadIdx.x == 0) { tree_copy32(out, edge_bytes + 32 * G.depth); if (index_dev) ((unsigned long long *)out)[4] = *index_dev; }
+  const uint64_t total = q * G.depth;
+  for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (uint64_t)gridDim.x * blockDim.x) {
+    const uint32_t k = (uint32_t)(t % G.depth); const uint64_t i = index_dev ? *index_dev : indices[t / G.depth];
+    if (i >= m) continue;
+    const uint64_t s = (i >> k) ^ 1;
+    const uint8_t *src = ((s + 1) << k) <= m ? G.nodes + 32 * (tree_off(G.cap_log, k) + s) : (s << k) >= m ? G.empty + 32 * k : edge_bytes + 32 * k;
+    tree_copy32(out + 64 + 32 * t, src);
+  }
+}
+// the tree goes back to state m, 1 <= m < n: the edge is written to the level arrays and nothing else; nodes beyond the new counts stay as stale bytes that no kernel
+// reads (k_tree_path and k_tree_append go by the counts)
+__global__ void __launch_bounds__(64) k_tree_rewind(TreeGeom G, uint64_t m) {
+  if (threadIdx.x) return;
+  tree_edge_walk(G, m, [&](uint32_t k, const Node &B) { tree_store(G.nodes + 32 * (tree_off(G.cap_log, k) + ((m - 1) >> k)), B); });
+}
+
 struct CommitmentTree::Impl {
   std::mutex mu; uint32_t depth = 0, cap_log = 0; uint64_t n = 0; DevBuf<uint8_t> nodes, empty, out, first /* k_tree_find's word */; std::vector<uint8_t> empty_host;
-  uint64_t launches = 0;
+  uint64_t launches = 0, state_launches = 0; DevBuf<uint8_t> q_in, q_out;   // past states: the sizes or indices of a call, and its answer (kept and grown)
+  static void grow(DevBuf<uint8_t> &b, size_t bytes) { if (b.size() < bytes) b = DevBuf<uint8_t>(std::max(bytes, 2 * b.size())); }
+  // the main stream is synchronised when a past-state entry returns or throws: nothing still reads the caller's arrays or writes the host vector then
+  struct SyncAtExit { ~SyncAtExit() { (void)hipStreamSynchronize(gpu().stream); } };
+  // [root | index | q paths] of state m >= 1 in one download: the indices from the host or (from_find, q = 1) from k_tree_find's word
+  void fetch_at(uint64_t m, const uint64_t *indices, size_t q, bool from_find, std::vector<uint8_t> &host) {
+    hipStream_t s = gpu().stream; const size_t bytes = 64 + 32 * q * depth; grow(q_out, bytes);
+    if (!from_find && q) { grow(q_in, 8 * q); HIP_CHECK(hipMemcpyAsync(q_in.get(), indices, 8 * q, hipMemcpyHostToDevice, s)); }
+    const unsigned nb = (unsigned)std::min<uint64_t>(std::max<uint64_t>(cdiv(q * depth, 256), 1), 256);
+    hipLaunchKernelGGL(k_tree_paths_at, dim3(nb), dim3(256), 0, s, geom(), m, from_find ? nullptr : (const unsigned long long *)q_in.get(),
+                       from_find ? (const unsigned long long *)first.get() : nullptr, (uint64_t)q, q_out.get()); state_launches++;
+    HIP_CHECK(hipGetLastError()); host.resize(bytes); q_out.download(host.data(), bytes);
+  }
   TreeGeom geom() const { return TreeGeom{nodes.get(), empty.get(), cap_log, depth}; }
   static size_t bytes_for(uint32_t cap_log, uint32_t depth) { return 32 * (size_t)(tree_off(cap_log, depth) + 1); }
   // room for n_new leaves: a new allocation of twice the capacity or more, every level copied over by the library's copy kernel
@@ -106,7 +186,7 @@ struct CommitmentTree::Impl {
     hipLaunchKernelGGL(k_tree_path, dim3(1), dim3(64), 0, gpu().stream, geom(), n, index, index_from_find ? (const unsigned long long *)first.get() : nullptr, out.get());
     HIP_CHECK(hipGetLastError()); host.resize(32 * (depth + 2)); out.download(host.data(), host.size());
   }
-  void find_async(const uint8_t leaf[32]) {
+  void find_async(const uint8_t leaf[32], uint64_t n) {                                           // among the first n leaves
     HIP_CHECK(hipMemsetAsync(first.get(), 0xff, 8, gpu().stream)); if (!n) return;
     uint4 t[2]; memcpy(t, leaf, 32); const unsigned nb = (unsigned)std::min<uint64_t>(cdiv(n, 256), 2048);
     hipLaunchKernelGGL(k_tree_find, dim3(nb), dim3(256), 0, gpu().stream, (const uint4 *)nodes.get(), n, t[0], t[1], (unsigned long long *)first.get());
@@ -125,6 +205,7 @@ CommitmentTree::~CommitmentTree() { try { LaneScope lane(0); std::lock_guard<std
 int CommitmentTree::depth() const { return (int)impl->depth; }
 uint64_t CommitmentTree::size() const { std::lock_guard<std::mutex> lk(impl->mu); return impl->n; }
 uint64_t CommitmentTree::launches() const { std::lock_guard<std::mutex> lk(impl->mu); return impl->launches; }
+uint64_t CommitmentTree::state_launches() const { std::lock_guard<std::mutex> lk(impl->mu); return impl->state_launches; }
 
 bool CommitmentTree::append(const uint8_t *leaves, size_t count) {
   Impl &d = *impl; std::lock_guard<std::mutex> lk(d.mu);
@@ -162,19 +243,71 @@ bool CommitmentTree::path(uint64_t index, uint8_t *siblings) {
 }
 bool CommitmentTree::find(const uint8_t leaf[32], uint64_t &index) {
   Impl &d = *impl; std::lock_guard<std::mutex> lk(d.mu); if (!d.n) return false;
-  LaneScope lane(0); std::lock_guard<std::mutex> gl(g_gpu_mutex); d.find_async(leaf); HIP_CHECK(hipGetLastError());
+  LaneScope lane(0); std::lock_guard<std::mutex> gl(g_gpu_mutex); d.find_async(leaf, d.n); HIP_CHECK(hipGetLastError());
   uint64_t got = 0; d.first.download((uint8_t *)&got, 8); if (got >= d.n) return false;
   index = got; return true;
 }
 bool CommitmentTree::snapshot(const uint8_t leaf[32], Snapshot &out) {
   Impl &d = *impl; std::lock_guard<std::mutex> lk(d.mu); out.size = d.n; out.path.assign(32 * d.depth, 0); out.index_bits.assign(d.depth, false); out.index = 0;
   if (!d.n) { memcpy(out.root, &d.empty_host[32 * d.depth], 32); return false; }
-  LaneScope lane(0); std::lock_guard<std::mutex> gl(g_gpu_mutex); std::vector<uint8_t> h; d.find_async(leaf); d.fetch(0, true, h);   // find, gather, one download
+  LaneScope lane(0); std::lock_guard<std::mutex> gl(g_gpu_mutex); std::vector<uint8_t> h; d.find_async(leaf, d.n); d.fetch(0, true, h);   // find, gather, one download
   memcpy(out.root, h.data() + 32 * (d.depth + 1), 32);
   uint64_t got; memcpy(&got, h.data(), 8); if (got >= d.n) return false;
   out.index = got; memcpy(out.path.data(), h.data() + 32, 32 * d.depth);
   for (uint32_t k = 0; k < d.depth; k++) out.index_bits[k] = (got >> k) & 1;
   return true;
+}
+
+// ---- past states: every entry checks its arguments before anything is queued, so a failing call writes nothing and changes nothing ----------------------------
+bool CommitmentTree::roots_at(const uint64_t *sizes, size_t q, uint8_t *out) {
+  Impl &d = *impl; std::lock_guard<std::mutex> lk(d.mu);
+  if (q && (!sizes || !out)) return false;
+  for (size_t i = 0; i < q; i++) if (sizes[i] > d.n) return false;
+  if (!q) return true;
+  LaneScope lane(0); std::lock_guard<std::mutex> gl(g_gpu_mutex); hipStream_t s = gpu().stream;
+  d.grow(d.q_in, 8 * q); d.grow(d.q_out, 32 * q); std::vector<uint8_t> h(32 * q); Impl::SyncAtExit sync;   // (the vector outlives the synchronise)
+  HIP_CHECK(hipMemcpyAsync(d.q_in.get(), sizes, 8 * q, hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(k_tree_roots_at, dim3((unsigned)cdiv(q, 64)), dim3(64), 0, s, d.geom(), (const unsigned long long *)d.q_in.get(), (uint64_t)q, d.q_out.get()); d.state_launches++;
+  HIP_CHECK(hipGetLastError()); d.q_out.download(h.data(), h.size());
+  memcpy(out, h.data(), h.size()); return true;
+}
+bool CommitmentTree::paths_at(uint64_t size, const uint64_t *indices, size_t q, uint8_t *siblings, uint8_t *root) {
+  Impl &d = *impl; std::lock_guard<std::mutex> lk(d.mu);
+  if (size > d.n || (q && (!indices || !siblings))) return false;
+  for (size_t i = 0; i < q; i++) if (indices[i] >= size) return false;
+  if (!size) { if (root) memcpy(root, &d.empty_host[32 * d.depth], 32); return true; }          // (q = 0 here: no index lies below 0)
+  if (!q && !root) return true;
+  LaneScope lane(0); std::lock_guard<std::mutex> gl(g_gpu_mutex); std::vector<uint8_t> h; Impl::SyncAtExit sync; d.fetch_at(size, indices, q, false, h);
+  if (q) memcpy(siblings, h.data() + 64, 32 * q * d.depth);
+  if (root) memcpy(root, h.data(), 32);
+  return true;
+}
+bool CommitmentTree::find_at(uint64_t size, const uint8_t leaf[32], uint64_t &index) {
+  Impl &d = *impl; std::lock_guard<std::mutex> lk(d.mu); if (size > d.n || !leaf || !size) return false;
+  LaneScope lane(0); std::lock_guard<std::mutex> gl(g_gpu_mutex); uint64_t got = 0; Impl::SyncAtExit sync; d.find_async(leaf, size); d.state_launches++; HIP_CHECK(hipGetLastError());
+  d.first.download((uint8_t *)&got, 8); if (got >= size) return false;
+  index = got; return true;
+}
+bool CommitmentTree::snapshot_at(uint64_t size, const uint8_t leaf[32], Snapshot &out) {
+  Impl &d = *impl; std::lock_guard<std::mutex> lk(d.mu); out.size = size; out.path.assign(32 * d.depth, 0); out.index_bits.assign(d.depth, false); out.index = 0;
+  memcpy(out.root, &d.empty_host[32 * d.depth], 32);
+  if (size > d.n || !size || !leaf) return false;                                                 // (a size the tree does not hold: the empty root, and false)
+  LaneScope lane(0); std::lock_guard<std::mutex> gl(g_gpu_mutex); std::vector<uint8_t> h; Impl::SyncAtExit sync;
+  d.find_async(leaf, size); d.state_launches++; d.fetch_at(size, nullptr, 1, true, h);            // find, edge walk and gather, one download
+  memcpy(out.root, h.data(), 32);
+  uint64_t got; memcpy(&got, h.data() + 32, 8); if (got >= size) return false;
+  out.index = got; memcpy(out.path.data(), h.data() + 64, 32 * d.depth);
+  for (uint32_t k = 0; k < d.depth; k++) out.index_bits[k] = (got >> k) & 1;
+  return true;
+}
+bool CommitmentTree::rewind(uint64_t size) {
+  Impl &d = *impl; std::lock_guard<std::mutex> lk(d.mu); if (size > d.n) return false;
+  if (size == d.n) return true;
+  if (!size) { d.n = 0; return true; }                                                            // the empty tree reads no node
+  LaneScope lane(0); std::lock_guard<std::mutex> gl(g_gpu_mutex); hipStream_t s = gpu().stream;
+  hipLaunchKernelGGL(k_tree_rewind, dim3(1), dim3(64), 0, s, d.geom(), size); d.state_launches++;
+  HIP_CHECK(hipGetLastError()); HIP_CHECK(hipStreamSynchronize(s));
+  d.n = size; return true;
 }
 
 }  // namespace zk

@@ -317,6 +317,24 @@ class Tree:
         i = ctypes.c_uint64(0); _check(lib().zkgpu_tree_find(ctypes.c_void_p(self.h), bytes(leaf), ctypes.byref(i))); return int(i.value)
     def launches(self):
         k = ctypes.c_uint64(0); _check(lib().zkgpu_test_tree_launches(ctypes.c_void_p(self.h), ctypes.byref(k))); return int(k.value)
+    # past states: state m = the tree of the first m leaves, 0 <= m <= size()
+    def roots_at(self, sizes):
+        """the roots of the states `sizes` (any order, repeats allowed), one launch -> [32-byte root]"""
+        m = np.ascontiguousarray(sizes, dtype=np.uint64).reshape(-1); q = int(m.size); out = ctypes.create_string_buffer(max(1, 32 * q))
+        _check(lib().zkgpu_tree_roots_at(ctypes.c_void_p(self.h), m.ctypes.data_as(ctypes.c_void_p) if q else None, ctypes.c_size_t(q), out)); return [out.raw[32 * i:32 * i + 32] for i in range(q)]
+    def paths_at(self, size, indices):
+        """-> ([siblings of leaf i in state `size`, leaf level first, for i in indices], the root of that state)"""
+        ix = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1); q = int(ix.size); d = self.depth; out = ctypes.create_string_buffer(max(1, 32 * q * d)); root = ctypes.create_string_buffer(32)
+        _check(lib().zkgpu_tree_paths_at(ctypes.c_void_p(self.h), ctypes.c_uint64(size), ix.ctypes.data_as(ctypes.c_void_p) if q else None, ctypes.c_size_t(q), out, root))
+        return [[out.raw[32 * (i * d + k):32 * (i * d + k) + 32] for k in range(d)] for i in range(q)], root.raw
+    def find_at(self, size, leaf):
+        """index of the first of the first `size` leaves equal to the blob; raises ZkGpuError if there is none"""
+        i = ctypes.c_uint64(0); _check(lib().zkgpu_tree_find_at(ctypes.c_void_p(self.h), ctypes.c_uint64(size), bytes(leaf), ctypes.byref(i))); return int(i.value)
+    def rewind(self, size):
+        """the tree goes back to its first `size` leaves"""
+        _check(lib().zkgpu_tree_rewind(ctypes.c_void_p(self.h), ctypes.c_uint64(size)))
+    def state_launches(self):
+        k = ctypes.c_uint64(0); _check(lib().zkgpu_test_tree_state_launches(ctypes.c_void_p(self.h), ctypes.byref(k))); return int(k.value)
     def close(self):
         if self.h: lib().zkgpu_tree_destroy(ctypes.c_void_p(self.h)); self.h = None
     def __del__(self):
@@ -364,6 +382,8 @@ class Zk:
         for f in ("verifyMintproof", "verifySendproof", "verifyRedeemproof", "verifyDepositproof"): getattr(L, f).restype = ctypes.c_bool
         for f in ("zkTreeRoot", "genDepositproofTree"): getattr(L, f).restype = ctypes.c_char_p
         L.zkTreeNew.restype = ctypes.c_void_p; L.zkTreeAppend.restype = ctypes.c_longlong; L.verifyDepositproofDepth.restype = ctypes.c_bool
+        for f in ("zkTreeRootAt", "genDepositproofTreeAt"): getattr(L, f).restype = ctypes.c_char_p
+        L.zkTreeRewind.restype = ctypes.c_longlong; L.zkTreeRootsAt.restype = ctypes.c_int
         self.L = L
     @staticmethod
     def hx(b): return ("0x" + bytes(b).hex()).encode()          # common.ToHex
@@ -432,6 +452,25 @@ class Zk:
         rt = ctypes.create_string_buffer(65)
         p = self.L.genDepositproofTree(ctypes.c_uint64(value), ctypes.c_uint64(value_old), self.hx(sn_old), self.hx(r_old), self.hx(sn), self.hx(r), self.hx(sns), self.hx(rs), self.hx(cmtB_old), self.hx(cmtB), ctypes.c_uint64(value_s),
                                        self.hx(pk), self.hx(sn_A_old), self.hx(cmtS), self.hx(sk), ctypes.c_void_p(t) if t else None, rt).decode()
+        return p, (bytes.fromhex(rt.value.decode()) if rt.value else None)
+    # include/zk_tree_states.h: the tree at past sizes, and its rewind
+    def TreeRootAt(self, t, size):
+        """-> the root of the first `size` leaves as big-endian bytes, None on failure"""
+        r = self.L.zkTreeRootAt(ctypes.c_void_p(t) if t else None, ctypes.c_longlong(size)); return bytes.fromhex(r.decode()) if r else None
+    def TreeRootsAt(self, t, sizes, out=None):
+        """-> [root as big-endian bytes], None on failure; out: a (q, 32) uint8 array to write into instead (then the return value is 0 / -1)"""
+        m = np.ascontiguousarray(sizes, dtype=np.int64).reshape(-1); q = int(m.size); buf = out if out is not None else np.zeros((max(1, q), 32), dtype=np.uint8)
+        rc = int(self.L.zkTreeRootsAt(ctypes.c_void_p(t) if t else None, m.ctypes.data_as(ctypes.c_void_p) if q else None, q, _bytes(buf)))
+        if out is not None: return rc
+        return [buf[i].tobytes() for i in range(q)] if rc == 0 else None
+    def TreeRewind(self, t, size):
+        """-> the new number of leaves, -1 on failure"""
+        return int(self.L.zkTreeRewind(ctypes.c_void_p(t) if t else None, ctypes.c_longlong(size)))
+    def GenDepositProofTreeAt(self, value, value_old, sn_old, r_old, sn, r, sns, rs, cmtB_old, cmtB, value_s, pk, sn_A_old, cmtS, sk, t, size):
+        """GenDepositProofTree against the first `size` leaves -> (proof hex, root the proof was made against as big-endian bytes, or None on failure)"""
+        rt = ctypes.create_string_buffer(65)
+        p = self.L.genDepositproofTreeAt(ctypes.c_uint64(value), ctypes.c_uint64(value_old), self.hx(sn_old), self.hx(r_old), self.hx(sn), self.hx(r), self.hx(sns), self.hx(rs), self.hx(cmtB_old), self.hx(cmtB), ctypes.c_uint64(value_s),
+                                         self.hx(pk), self.hx(sn_A_old), self.hx(cmtS), self.hx(sk), ctypes.c_void_p(t) if t else None, ctypes.c_longlong(size), rt).decode()
         return p, (bytes.fromhex(rt.value.decode()) if rt.value else None)
     def VerifyDepositProofDepth(self, depth, proof, RT, pk, cmtb_old, sn_old, cmtb, sns):
         return bool(self.L.verifyDepositproofDepth(int(depth), proof.encode(), self.hx(RT), self.hx(pk), self.hx(cmtb_old), self.hx(sn_old), self.hx(cmtb), self.hx(sns)))

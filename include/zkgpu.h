@@ -208,6 +208,15 @@ int zkgpu_tree_root(zkgpu_tree *t, uint8_t root[32]);
 int zkgpu_tree_path(zkgpu_tree *t, uint64_t index, uint8_t *siblings /* depth x 32, leaf level first */);
 int zkgpu_tree_find(zkgpu_tree *t, const uint8_t leaf[32], uint64_t *index); /* the first index holding the blob; ZKGPU_ERR_ARG if absent */
 int zkgpu_test_tree_launches(zkgpu_tree *t, uint64_t *launches);            /* test entry: append kernels launched for this tree so far */
+/* Past states (DESIGN.md "Past states of the commitment tree"; the drop-in level is zk_tree_states.h).  State m is the tree of the first m leaves, 0 <= m <= size.
+ * Each entry checks its arguments before anything runs — ZKGPU_ERR_ARG for a size above the tree's size, an index that is not below its size, a null pointer; nothing
+ * is written and nothing changes then — and is at most two kernel launches and one download whatever q is.  q = 0 is a valid call. */
+int zkgpu_tree_roots_at(zkgpu_tree *t, const uint64_t *sizes, size_t q, uint8_t *roots /* q x 32 */);   /* sizes in any order, repeats allowed; one launch */
+int zkgpu_tree_paths_at(zkgpu_tree *t, uint64_t size, const uint64_t *indices, size_t q, uint8_t *siblings /* q x depth x 32, leaf level first */,
+                        uint8_t root[32] /* the root of state `size`; may be NULL */);
+int zkgpu_tree_find_at(zkgpu_tree *t, uint64_t size, const uint8_t leaf[32], uint64_t *index);   /* the first of the first `size` leaves holding the blob */
+int zkgpu_tree_rewind(zkgpu_tree *t, uint64_t size);                        /* the tree becomes state `size`: the leaves from `size` on are gone */
+int zkgpu_test_tree_state_launches(zkgpu_tree *t, uint64_t *launches);      /* test entry: kernels launched by the four entries above and by the proofs at a past size */
 /* test entry, host only: root (if root != NULL) and, if path != NULL, the path of `index` by notes.cpp's tree_levels */
 int zkgpu_test_tree_host(int depth, const uint8_t *leaves, size_t n, uint64_t index, uint8_t root[32], uint8_t *path);
 
