@@ -16,7 +16,9 @@
 #include <cstdlib>
 #include <cstring>
 #include <atomic>
+#include <array>
 #include <map>
+#include <set>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -32,6 +34,7 @@
 #include "../../include/zk_tree.h"
 #include "../../include/zk_tree_states.h"
 #include "../../include/zk_roots.h"
+#include "../../include/zk_spent.h"
 #include "../../include/zkgpu.h"
 #include "blockmaze_circuits.hpp"
 #include "groth16.hpp"
@@ -463,6 +466,22 @@ template <class Fn> static int guarded_tree(zkgpu_tree *t, Fn fn) {
   catch (const std::exception &e) { zkgpu_set_error(e.what()); return ZKGPU_ERR_RUNTIME; }
   catch (...) { zkgpu_set_error("unknown error"); return ZKGPU_ERR_RUNTIME; }
 }
+
+// the resident set of spent serial numbers: it locks for itself as the tree does (its own mutex, then the device mutex: gpu_snset.hip)
+struct zkgpu_snset { SpentSet s; zkgpu_snset(const uint8_t *exempt, int log2_slots, const uint64_t *seed) : s(exempt, log2_slots, seed) {} };
+template <class Fn> static int guarded_snset(zkgpu_snset *s, Fn fn) {
+  try {
+    if (!gpu_available()) { zkgpu_set_error("no HIP device visible; libzkgpu has no CPU fallback"); return ZKGPU_ERR_NO_DEVICE; }
+    if (!s) { zkgpu_set_error("no spent set"); return ZKGPU_ERR_ARG; }
+    return fn();
+  }
+  catch (const std::exception &e) { zkgpu_set_error(e.what()); return ZKGPU_ERR_RUNTIME; }
+  catch (...) { zkgpu_set_error("unknown error"); return ZKGPU_ERR_RUNTIME; }
+}
+// the serial number a record spends, as the 32 bytes of its common.Hash: snold (args[3]) for deposit, args[1] for mint, send and redeem; the set's key is what
+// common.BytesToAddress keeps of it, bytes 12..31
+static const uint8_t *record_sn(const zk_block_record &r) { return r.kind == ZK_KIND_DEPOSIT ? r.args[3] : r.args[1]; }
+static void sn_keys(const uint8_t *sns, size_t n, std::vector<uint8_t> &keys) { keys.resize(20 * n); for (size_t i = 0; i < n; i++) memcpy(&keys[20 * i], sns + 32 * i + 12, 20); }
 
 extern "C" {
 char *zkgpu_abi_genCMT(uint64_t value, char *sn_string, char *r_string) {
@@ -1555,6 +1574,102 @@ int verifyBlockRecordsRoots(const zk_block_record *recs, int n, const zk_cmt_lis
   }
   catch (const std::exception &e) { return fail(e.what()); }
   catch (...) { return fail("unknown error"); }
+}
+
+// ---- the resident set of spent serial numbers (DESIGN.md "Spent serial numbers"; include/zkgpu.h, include/zk_spent.h) ----------------------------------------
+static zkgpu_snset *snset_create(const uint8_t *exempt, int log2_slots, const uint64_t *seed) {
+  zkgpu_snset *s = nullptr;
+  try {
+    if (!gpu_available()) { zkgpu_set_error("no HIP device visible; libzkgpu has no CPU fallback"); return nullptr; }
+    s = new zkgpu_snset(exempt, log2_slots, seed);
+  }
+  catch (const std::exception &e) { zkgpu_set_error(e.what()); } catch (...) { zkgpu_set_error("unknown error"); }
+  return s;
+}
+zkgpu_snset *zkgpu_snset_create(const uint8_t exempt[20]) { return snset_create(exempt, 0, nullptr); }
+zkgpu_snset *zkgpu_test_snset_create(int log2_slots, uint64_t seed, const uint8_t exempt[20]) {
+  if (log2_slots < 4 || log2_slots > 31) { zkgpu_set_error("spent set: a table has 2^4 to 2^31 slots"); return nullptr; }
+  return snset_create(exempt, log2_slots, &seed); }
+void zkgpu_snset_destroy(zkgpu_snset *s) { try { delete s; } catch (...) {} }
+int zkgpu_snset_size(zkgpu_snset *s, uint64_t *n) { return guarded_snset(s, [&] { if (!n) return ZKGPU_ERR_ARG; *n = s->s.size(); return ZKGPU_OK; }); }
+int zkgpu_snset_spend(zkgpu_snset *s, const uint8_t *keys, const uint8_t *mask, size_t n, int commit, uint8_t *conflict, uint64_t *size_out) { return guarded_snset(s, [&] {
+  if (!s->s.spend(keys, mask, n, commit != 0, conflict, size_out)) { zkgpu_set_error("spent set: a null pointer, or the log would reach 2^32 - 2 entries"); return ZKGPU_ERR_ARG; }
+  return ZKGPU_OK; }); }
+int zkgpu_snset_query(zkgpu_snset *s, uint64_t size, const uint8_t *keys, size_t q, uint64_t *index) { return guarded_snset(s, [&] {
+  if (!s->s.query(size, keys, q, index)) { zkgpu_set_error("spent set: size " + std::to_string(size) + " is above the set's size, or a null pointer"); return ZKGPU_ERR_ARG; }
+  return ZKGPU_OK; }); }
+int zkgpu_snset_rewind(zkgpu_snset *s, uint64_t size) { return guarded_snset(s, [&] {
+  if (!s->s.rewind(size)) { zkgpu_set_error("spent set: cannot rewind to " + std::to_string(size) + " keys, the set holds fewer"); return ZKGPU_ERR_ARG; }
+  return ZKGPU_OK; }); }
+int zkgpu_snset_read_log(zkgpu_snset *s, uint64_t first, uint64_t count, uint8_t *keys) { return guarded_snset(s, [&] {
+  if (!s->s.read_log(first, count, keys)) { zkgpu_set_error("spent set: the range leaves the log, or a null pointer"); return ZKGPU_ERR_ARG; }
+  return ZKGPU_OK; }); }
+int zkgpu_test_snset_slots(zkgpu_snset *s, uint32_t *slots, uint64_t *n_slots, uint64_t *seed, uint64_t *tombstones) { return guarded_snset(s, [&] {
+  if (!n_slots || !seed || !tombstones) return ZKGPU_ERR_ARG;
+  std::vector<uint32_t> t; uint64_t sd = 0, tb = 0; s->s.table(t, sd, tb);
+  if (slots) { if (*n_slots != t.size()) { zkgpu_set_error("spent set: the table has " + std::to_string(t.size()) + " slots"); return ZKGPU_ERR_ARG; } memcpy(slots, t.data(), 4 * t.size()); }
+  *n_slots = t.size(); *seed = sd; *tombstones = tb; return ZKGPU_OK; }); }
+int zkgpu_test_snset_launches(uint64_t *launches) { if (!launches) return ZKGPU_ERR_ARG; *launches = SpentSet::launches(); return ZKGPU_OK; }
+// the model: for each record in turn, Exist -> conflict, otherwise (commit) CreateAccount.  A check-only call inserts nothing, so what it remembers of the call itself
+// is kept apart from the set.
+int zkgpu_test_snset_host(const uint8_t *resident, size_t n_resident, const uint8_t exempt[20], const uint8_t *keys, const uint8_t *mask, size_t n, int commit,
+                          uint8_t *conflict, uint8_t *appended, size_t *n_appended) { return guarded_host([&] {
+  if ((n_resident && !resident) || (n && (!keys || !conflict || (commit && !appended))) || !n_appended) return ZKGPU_ERR_ARG;
+  typedef std::array<uint8_t, 20> Key; auto key = [](const uint8_t *p) { Key k; memcpy(k.data(), p, 20); return k; };
+  std::set<Key> state, seen; for (size_t i = 0; i < n_resident; i++) state.insert(key(resident + 20 * i));
+  size_t added = 0;
+  for (size_t i = 0; i < n; i++) {
+    const Key k = key(keys + 20 * i); conflict[i] = 0;
+    if ((mask && !mask[i]) || (exempt && !memcmp(k.data(), exempt, 20))) continue;
+    if (state.count(k)) { conflict[i] = 1; continue; }                                            // statedb.Exist: "sn is already used"
+    if (seen.count(k)) { conflict[i] = 2; continue; }                                             // ... by an earlier transaction of this block
+    seen.insert(k); if (commit) memcpy(appended + 20 * added++, k.data(), 20);                    // CreateAccount
+  }
+  *n_appended = added; return ZKGPU_OK; }); }
+
+zk_snset *zkSnSetNew(const uint8_t *exempt_sn) { return zkgpu_snset_create(exempt_sn ? exempt_sn + 12 : nullptr); }
+void zkSnSetFree(zk_snset *set) { zkgpu_snset_destroy(set); }
+long long zkSnSetSize(zk_snset *set) { uint64_t n = 0; return zkgpu_snset_size(set, &n) == ZKGPU_OK ? (long long)n : -1; }
+int zkSnSetContains(zk_snset *set, long long size, const uint8_t *sns, int n, unsigned char *in) {
+  const int rc = guarded_snset(set, [&] {
+    if (n < 0 || (n && (!sns || !in))) { zkgpu_set_error("zkSnSetContains: a negative count or a null pointer"); return ZKGPU_ERR_ARG; }
+    std::vector<uint8_t> keys; sn_keys(sns, (size_t)n, keys); std::vector<uint64_t> index((size_t)n);
+    if (!set->s.query(size < 0 ? 0 : (uint64_t)size, keys.data(), (size_t)n, index.data(), size < 0)) { zkgpu_set_error("zkSnSetContains: the set does not hold " + std::to_string(size) + " keys"); return ZKGPU_ERR_ARG; }
+    for (int i = 0; i < n; i++) in[i] = index[i] != UINT64_MAX;
+    return ZKGPU_OK; });
+  if (rc != ZKGPU_OK) { fprintf(stderr, "libzkgpu: zkSnSetContains: %s\n", zkgpu_last_error()); return -1; }
+  return 0;
+}
+long long zkSnSetRewind(zk_snset *set, long long size) {
+  const int rc = guarded_snset(set, [&] {
+    if (size < 0 || !set->s.rewind((uint64_t)size)) { zkgpu_set_error("zkSnSetRewind: the set does not hold " + std::to_string(size) + " keys"); return ZKGPU_ERR_ARG; }
+    return ZKGPU_OK; });
+  if (rc != ZKGPU_OK) { fprintf(stderr, "libzkgpu: zkSnSetRewind: %s\n", zkgpu_last_error()); return -1; }
+  return size;
+}
+long long zkSnSetSpend(zk_snset *set, const uint8_t *sns, int n, int commit, unsigned char *spent) {
+  uint64_t size = 0;
+  const int rc = guarded_snset(set, [&] {
+    if (n < 0 || (n && (!sns || !spent))) { zkgpu_set_error("zkSnSetSpend: a negative count or a null pointer"); return ZKGPU_ERR_ARG; }
+    std::vector<uint8_t> keys, conflict((size_t)n); sn_keys(sns, (size_t)n, keys);
+    if (!set->s.spend(keys.data(), nullptr, (size_t)n, commit != 0, conflict.data(), &size)) { zkgpu_set_error("zkSnSetSpend: the log would reach 2^32 - 2 entries"); return ZKGPU_ERR_ARG; }
+    for (int i = 0; i < n; i++) spent[i] = conflict[i] != 0;
+    return ZKGPU_OK; });
+  if (rc != ZKGPU_OK) { fprintf(stderr, "libzkgpu: zkSnSetSpend: %s\n", zkgpu_last_error()); return -1; }
+  return (long long)size;
+}
+int verifyBlockFull(const zk_block_record *recs, int n, const zk_cmt_lists *l, const int32_t *list_of, zk_snset *set, int commit, unsigned char *ok, long long *size_out) {
+  const int accepted = verifyBlockRecordsRoots(recs, n, l, list_of, ok); if (accepted < 0 || !set) return accepted;
+  uint64_t size = 0; std::vector<uint8_t> conflict;
+  const int rc = guarded_snset(set, [&] {
+    std::vector<uint8_t> keys((size_t)20 * n); conflict.resize((size_t)n);
+    { HostSpan span("host.sn_keys"); for (int i = 0; i < n; i++) memcpy(&keys[20 * (size_t)i], record_sn(recs[i]) + 12, 20); }
+    if (!set->s.spend(keys.data(), ok, (size_t)n, commit != 0, conflict.data(), &size)) { zkgpu_set_error("the log would reach 2^32 - 2 entries"); return ZKGPU_ERR_ARG; }
+    return ZKGPU_OK; });
+  if (rc != ZKGPU_OK) { fprintf(stderr, "libzkgpu: verifyBlockFull: %s\n", zkgpu_last_error()); for (int i = 0; i < n; i++) ok[i] = 0; return -1; }
+  int still = 0; for (int i = 0; i < n; i++) { if (conflict[i]) ok[i] = 0; still += ok[i] != 0; }
+  if (size_out) *size_out = (long long)size;
+  return still;
 }
 
 // the reference's symbol names, exported by libzkgpu.so itself (the four libzk_*.so forward to the zkgpu_abi_* names above)

@@ -197,6 +197,27 @@ class CommitmentTree {
   struct Impl; std::unique_ptr<Impl> impl;
 };
 
+// The set of spent serial numbers resident in HBM (gpu_snset.hip; DESIGN.md "Spent serial numbers"): an append-only log of distinct 20-byte keys in insertion order
+// and an open-addressing index over it; state m = the first m log entries.  An optional exempt key is never in conflict and never inserted.  One mutex per set (taken
+// before the device mutex): spend, query, rewind and read_log are each atomic with respect to the others.  false = a bad argument (a size above size(), a null
+// pointer, a log that would reach 2^32 - 2 entries): nothing is written and nothing changes.  There is no host set.
+class SpentSet {
+ public:
+  explicit SpentSet(const uint8_t *exempt /* 20 bytes, or null */, int log2_slots = 0 /* tests: a table of 2^4 slots or more; 0 = 2^10 */, const uint64_t *seed = nullptr /* tests; null = getrandom */);
+  ~SpentSet();
+  uint64_t size() const;
+  // the reference's check-then-insert loop in record order (keys: n x 20 bytes; mask: n bytes or null = all in): conflict[i] = 0 skipped (masked out, exempt) or
+  // fresh, 1 the key was in the set before the call, 2 an earlier masked-in record of the call has it.  commit: the fresh keys are appended in record order;
+  // otherwise the set is afterwards what it was, bit for bit.  One upload, at most one rebuild, three launches and one download whatever n is.
+  bool spend(const uint8_t *keys, const uint8_t *mask, size_t n, bool commit, uint8_t *conflict, uint64_t *size_out /* or null */);
+  bool query(uint64_t size, const uint8_t *keys, size_t q, uint64_t *index, bool current = false);   // index[i] = the key's position in the log if below `size` (current: below size()), else 2^64 - 1
+  bool rewind(uint64_t size);                                                 // the set becomes state `size`
+  bool read_log(uint64_t first, uint64_t count, uint8_t *out);                // keys first .. first + count - 1 of the log, 20 bytes each
+  void table(std::vector<uint32_t> &slots, uint64_t &seed, uint64_t &tombstones);   // tests: the index as it lies in device memory
+  static uint64_t launches();                                                 // kernels launched by all sets of the process so far (tests)
+  struct Impl; std::unique_ptr<Impl> impl;
+};
+
 // The roots of many independent commitment lists (gpu_list_roots.hip): list i = leaves[first .. first + count) of one shared array, roots[i] = the root of the tree
 // above over that list alone (notes.cpp: merkle_root), in the caller's order.  hash_order: leaves and roots as the bytes of the common.Hash instead of blob order.
 // The caller has checked the arguments (depth 1..32, every range inside the array, count <= 2^depth) and holds the device mutex; runs on the main stream and

@@ -347,6 +347,63 @@ def tree_host(depth, leaves, index=None, want_root=True):
     _check(lib().zkgpu_test_tree_host(int(depth), bytes(buf) if n else None, ctypes.c_size_t(n), ctypes.c_uint64(index or 0), root, path))
     return (root.raw if want_root else None), ([path.raw[32 * k:32 * k + 32] for k in range(depth)] if path is not None else None)
 
+# ---- the set of spent serial numbers resident in HBM (include/zkgpu.h "the set of spent serial numbers"; the drop-in level is include/zk_spent.h) ----
+ABSENT = (1 << 64) - 1
+def _keys20(keys):
+    """a list of 20-byte strings, one bytes object of n x 20 bytes, or an (n, 20) uint8 array -> (bytes, n)"""
+    buf = keys.tobytes() if isinstance(keys, np.ndarray) else bytes(keys) if isinstance(keys, (bytes, bytearray)) else b"".join(bytes(k) for k in keys)
+    assert len(buf) % 20 == 0; return buf, len(buf) // 20
+class SpentSet:
+    """append-only set of 20-byte keys on the device: the log of distinct keys in insertion order and an index over it; state m = the first m keys"""
+    def __init__(self, exempt=None, log2_slots=None, seed=0):
+        """log2_slots: the test entry (a table of 2^log2_slots slots and the given seed); otherwise 2^10 slots and a seed from getrandom"""
+        L = lib(); L.zkgpu_snset_create.restype = ctypes.c_void_p; L.zkgpu_test_snset_create.restype = ctypes.c_void_p; ex = bytes(exempt) if exempt is not None else None
+        self.h = L.zkgpu_snset_create(ex) if log2_slots is None else L.zkgpu_test_snset_create(int(log2_slots), ctypes.c_uint64(seed), ex)
+        if not self.h: raise ZkGpuError(lib().zkgpu_last_error().decode())
+    def size(self):
+        n = ctypes.c_uint64(0); _check(lib().zkgpu_snset_size(ctypes.c_void_p(self.h), ctypes.byref(n))); return int(n.value)
+    def spend(self, keys, mask=None, commit=True):
+        """-> ([conflict code per record: 0 fresh or skipped, 1 in the set before the call, 2 an earlier masked-in record of the call has it], the size after the call)"""
+        buf, n = _keys20(keys); m = bytes(bytearray(int(bool(x)) for x in mask)) if mask is not None else None; assert m is None or len(m) == n
+        out = ctypes.create_string_buffer(max(1, n)); size = ctypes.c_uint64(0)
+        _check(lib().zkgpu_snset_spend(ctypes.c_void_p(self.h), buf, m, ctypes.c_size_t(n), int(bool(commit)), out, ctypes.byref(size))); return list(out.raw[:n]), int(size.value)
+    def query(self, size, keys):
+        """-> [position of the key in the log if it is below `size`, else None]"""
+        buf, q = _keys20(keys); out = (ctypes.c_uint64 * max(1, q))()
+        _check(lib().zkgpu_snset_query(ctypes.c_void_p(self.h), ctypes.c_uint64(size), buf, ctypes.c_size_t(q), out)); return [None if out[i] == ABSENT else int(out[i]) for i in range(q)]
+    def rewind(self, size): _check(lib().zkgpu_snset_rewind(ctypes.c_void_p(self.h), ctypes.c_uint64(size)))
+    def read_log(self, first=0, count=None):
+        """-> [20-byte key] of log entries first .. first + count - 1 (count None: to the end)"""
+        count = self.size() - first if count is None else count; out = ctypes.create_string_buffer(max(1, 20 * count))
+        _check(lib().zkgpu_snset_read_log(ctypes.c_void_p(self.h), ctypes.c_uint64(first), ctypes.c_uint64(count), out)); return [out.raw[20 * i:20 * i + 20] for i in range(count)]
+    def slots(self):
+        """test entry -> (the table as a uint32 array, the seed, the host's tombstone count)"""
+        n = ctypes.c_uint64(0); seed = ctypes.c_uint64(0); tombs = ctypes.c_uint64(0); h = ctypes.c_void_p(self.h)
+        _check(lib().zkgpu_test_snset_slots(h, None, ctypes.byref(n), ctypes.byref(seed), ctypes.byref(tombs))); t = np.zeros(int(n.value), dtype=np.uint32)
+        _check(lib().zkgpu_test_snset_slots(h, t.ctypes.data_as(ctypes.c_void_p), ctypes.byref(n), ctypes.byref(seed), ctypes.byref(tombs))); return t, int(seed.value), int(tombs.value)
+    def close(self):
+        if self.h: lib().zkgpu_snset_destroy(ctypes.c_void_p(self.h)); self.h = None
+    def __del__(self):
+        try: self.close()
+        except Exception: pass
+def snset_launches():
+    """kernels launched by all spent sets of this process so far"""
+    k = ctypes.c_uint64(0); _check(lib().zkgpu_test_snset_launches(ctypes.byref(k))); return int(k.value)
+def snset_host(resident, exempt, keys, mask=None, commit=True):
+    """zkgpu_test_snset_host: the plain sequential loop, no device needed -> ([conflict code], [appended key])"""
+    rb, nr = _keys20(resident); kb, n = _keys20(keys); m = bytes(bytearray(int(bool(x)) for x in mask)) if mask is not None else None
+    out = ctypes.create_string_buffer(max(1, n)); app = ctypes.create_string_buffer(max(1, 20 * n)); na = ctypes.c_size_t(0)
+    _check(lib().zkgpu_test_snset_host(rb if nr else None, ctypes.c_size_t(nr), bytes(exempt) if exempt is not None else None, kb if n else None, m, ctypes.c_size_t(n), int(bool(commit)), out, app, ctypes.byref(na)))
+    return list(out.raw[:n]), [app.raw[20 * i:20 * i + 20] for i in range(int(na.value))]
+def snset_home(key, seed, n_slots):
+    """the documented mix (include/zkgpu.h): the home slot of a 20-byte key in a table of n_slots slots"""
+    M = (1 << 64) - 1; h = seed
+    for k in range(5): h = ((h ^ int.from_bytes(key[4 * k:4 * k + 4], "little")) * 0x9E3779B97F4A7C15) & M; h ^= h >> 32
+    h = (h * 0xD6E8FEB86659FD93) & M; h ^= h >> 32; return h & (n_slots - 1)
+def record_sn(rec):
+    """the serial number a record (RECORD_DTYPE) spends, the 32 bytes of its common.Hash: snold = args[3] for deposit, args[1] for mint, send and redeem; the set's key is [12:]"""
+    return bytes(rec["args"][3 if int(rec["kind"]) == KIND["deposit"] else 1])
+
 # ---- the roots of many commitment lists (include/zkgpu.h "the roots of many commitment lists"; the drop-in level is include/zk_roots.h) ----
 def _leaf_array(leaves):
     """leaves: an (n, 32) uint8 array, one bytes object of n x 32 bytes, or a list of 32-byte strings -> flat uint8 array"""
@@ -434,6 +491,27 @@ class Zk:
         l, keep = _cmt_lists(cmts, lists) if lists is not None else (None, None); lo = np.ascontiguousarray(list_of, dtype=np.int32); assert lo.shape == (n,)
         ok = (ctypes.c_ubyte * max(1, n))(); self.L.verifyBlockRecordsRoots.restype = ctypes.c_int
         rc = self.L.verifyBlockRecordsRoots(ptr, n, ctypes.byref(l) if l is not None else None, lo.ctypes.data_as(ctypes.c_void_p) if n else None, ok); return rc, [bool(ok[i]) for i in range(n)]
+    # include/zk_spent.h: the resident set of spent serial numbers at the drop-in level (serial numbers as the 32 bytes of their common.Hash)
+    def SnSetNew(self, exempt_sn=None):
+        self.L.zkSnSetNew.restype = ctypes.c_void_p; return self.L.zkSnSetNew(bytes(exempt_sn) if exempt_sn is not None else None)   # None on failure
+    def SnSetFree(self, s): self.L.zkSnSetFree(ctypes.c_void_p(s))
+    def SnSetSize(self, s): self.L.zkSnSetSize.restype = ctypes.c_longlong; return int(self.L.zkSnSetSize(ctypes.c_void_p(s) if s else None))
+    def SnSetContains(self, s, sns, size=-1):
+        """-> [bool], None on failure"""
+        buf = b"".join(bytes(x) for x in sns); n = len(sns); out = ctypes.create_string_buffer(max(1, n))
+        rc = self.L.zkSnSetContains(ctypes.c_void_p(s) if s else None, ctypes.c_longlong(size), buf, n, out); return [bool(b) for b in out.raw[:n]] if rc == 0 else None
+    def SnSetRewind(self, s, size): self.L.zkSnSetRewind.restype = ctypes.c_longlong; return int(self.L.zkSnSetRewind(ctypes.c_void_p(s) if s else None, ctypes.c_longlong(size)))
+    def SnSetSpend(self, s, sns, commit=True):
+        """-> (the size after the call or -1, [spent?])"""
+        buf = b"".join(bytes(x) for x in sns); n = len(sns); out = ctypes.create_string_buffer(max(1, n)); self.L.zkSnSetSpend.restype = ctypes.c_longlong
+        size = int(self.L.zkSnSetSpend(ctypes.c_void_p(s) if s else None, buf, n, int(bool(commit)), out)); return size, [bool(b) for b in out.raw[:n]]
+    def VerifyBlockFull(self, items, cmts, lists, list_of, s, commit):
+        """include/zk_spent.h: VerifyBlockRecordsRoots, then the serial numbers of the accepted records against the set `s` (None: no set) -> (accepted, [bool], size after or None)"""
+        recs = items if isinstance(items, np.ndarray) else records_from_items(items); recs, ptr, n = _recs(recs)
+        l, keep = _cmt_lists(cmts, lists) if lists is not None else (None, None); lo = np.ascontiguousarray(list_of, dtype=np.int32) if list_of is not None else None; assert lo is None or lo.shape == (n,)
+        ok = (ctypes.c_ubyte * max(1, n))(); size = ctypes.c_longlong(-7); self.L.verifyBlockFull.restype = ctypes.c_int
+        rc = self.L.verifyBlockFull(ptr, n, ctypes.byref(l) if l is not None else None, lo.ctypes.data_as(ctypes.c_void_p) if lo is not None and n else None, ctypes.c_void_p(s) if s else None, int(bool(commit)), ok, ctypes.byref(size))
+        return rc, [bool(ok[i]) for i in range(n)], (None if size.value == -7 else int(size.value))
     def GenRedeemProof(self, value, value_old, sn_old, r_old, sn, r, cmtA_old, cmtA, value_s, sk):
         return self.L.genRedeemproof(ctypes.c_uint64(value), ctypes.c_uint64(value_old), self.hx(sn_old), self.hx(r_old), self.hx(sn), self.hx(r), self.hx(cmtA_old), self.hx(cmtA), ctypes.c_uint64(value_s), self.hx(sk)).decode()
     def VerifyRedeemProof(self, proof, cmtA_old, sn_old, cmtA, value_s): return bool(self.L.verifyRedeemproof(proof.encode(), self.hx(cmtA_old), self.hx(sn_old), self.hx(cmtA), ctypes.c_uint64(value_s)))

@@ -232,6 +232,37 @@ int zkgpu_list_roots(int depth, const uint8_t *leaves, size_t n_leaves, const zk
 int zkgpu_test_list_roots_host(int depth, const uint8_t *leaves, size_t n_leaves, const zkgpu_leaf_range *lists, size_t n_lists, int hash_order, uint8_t *roots);
 int zkgpu_test_list_roots_launches(uint64_t *launches);
 
+/* ---- the set of spent serial numbers resident in HBM (DESIGN.md "Spent serial numbers"; the drop-in level is zk_spent.h) ------------------------------------
+ * An append-only log of distinct 20-byte keys in insertion order and an index over it; state m is the first m log entries, 0 <= m <= size.  The index is an
+ * open-addressing table of 32-bit slots (a power of two of them, 2^10 at least), linear probing: a slot holds 0 (empty), 0xFFFFFFFF (a tombstone, left by a rewind) or
+ * log index + 1.  The home slot of a key: with w0..w4 the key's bytes as five little-endian 32-bit words and seed the set's 64-bit seed (getrandom at creation), in
+ * 64-bit arithmetic
+ *     h = seed;  for k = 0..4: h = (h ^ w_k) * 0x9E3779B97F4A7C15, h ^= h >> 32;  h = h * 0xD6E8FEB86659FD93, h ^= h >> 32;  home = h & (slots - 1).
+ * Live entries + tombstones + the incoming batch stay at or below half of the slots: otherwise the table is first rebuilt at the smallest sufficient size.
+ * ZKGPU_ERR_ARG, with nothing written and nothing changed, for a size above the current size, a null pointer, or a log that would reach 2^32 - 2 entries.  Entries of
+ * one set are atomic with respect to each other and may be called from any thread.  There is no host set. */
+typedef struct zkgpu_snset zkgpu_snset;
+zkgpu_snset *zkgpu_snset_create(const uint8_t exempt[20] /* or NULL */);     /* exempt: a key that is never in conflict and never inserted; NULL + zkgpu_last_error() on failure */
+void zkgpu_snset_destroy(zkgpu_snset *s);
+int zkgpu_snset_size(zkgpu_snset *s, uint64_t *n);
+/* The check-then-insert loop of core/state_processor.go:106-163 in record order.  keys: n x 20 bytes; mask: n bytes, or NULL = every record masked in.  Record i is
+ * skipped with conflict[i] = 0 if mask[i] == 0 or its key is the exempt key; otherwise conflict[i] = 1 if the key was in the set before the call, else 2 if an earlier
+ * record j < i with mask[j] != 0 has the same key, else 0 — and then, if commit != 0, the key is appended to the log (in record order).  size_out (may be NULL): the
+ * size after the call.  commit == 0 leaves the set unchanged bit for bit, index included.  One upload, at most one rebuild, three launches, one download. */
+int zkgpu_snset_spend(zkgpu_snset *s, const uint8_t *keys, const uint8_t *mask, size_t n, int commit, uint8_t *conflict, uint64_t *size_out);
+int zkgpu_snset_query(zkgpu_snset *s, uint64_t size, const uint8_t *keys, size_t q, uint64_t *index /* position in the log if below `size`, else UINT64_MAX = absent */);
+int zkgpu_snset_rewind(zkgpu_snset *s, uint64_t size);                       /* the set becomes state `size` */
+int zkgpu_snset_read_log(zkgpu_snset *s, uint64_t first, uint64_t count, uint8_t *keys /* count x 20 */);   /* to persist the set, and for tests */
+/* test entries: a set with a table of 2^log2_slots slots (4 .. 31; it still grows) and a given seed; the table as it lies in device memory (slots may be NULL: the
+ * three numbers alone; otherwise room for *n_slots words as a first call reported them); the process-wide number of kernel launches of all sets so far; and the model
+ * the kernels are tested against — stateless, host only, the plain sequential loop: resident = the keys in the set (n_resident x 20), appended receives the keys a
+ * commit adds, in order (room for n x 20), n_appended their number */
+zkgpu_snset *zkgpu_test_snset_create(int log2_slots, uint64_t seed, const uint8_t exempt[20]);
+int zkgpu_test_snset_slots(zkgpu_snset *s, uint32_t *slots, uint64_t *n_slots, uint64_t *seed, uint64_t *tombstones);
+int zkgpu_test_snset_launches(uint64_t *launches);
+int zkgpu_test_snset_host(const uint8_t *resident, size_t n_resident, const uint8_t exempt[20], const uint8_t *keys, const uint8_t *mask, size_t n, int commit,
+                          uint8_t *conflict, uint8_t *appended, size_t *n_appended);
+
 #ifdef __cplusplus
 }
 #endif
