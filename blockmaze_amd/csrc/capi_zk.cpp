@@ -35,6 +35,7 @@
 #include "../../include/zk_tree_states.h"
 #include "../../include/zk_roots.h"
 #include "../../include/zk_spent.h"
+#include "../../include/zk_proof_cache.h"
 #include "../../include/zkgpu.h"
 #include "blockmaze_circuits.hpp"
 #include "groth16.hpp"
@@ -77,7 +78,8 @@ typedef std::vector<std::shared_ptr<ProverUnit>> UnitList;
 struct ProverSlot { FileStamp stamp; std::vector<std::shared_ptr<const UnitList>> units /* one list per device slot, built on first use */;
     std::vector<uint8_t> building /* a caller is loading this device's pool */; std::atomic<unsigned> next{0}; };
 struct VkSlot { FileStamp stamp; std::shared_ptr<PreparedVerifyingKey> vk; std::shared_ptr<BatchVerifier> gpu;
-  std::shared_ptr<BlockVerifier> block; int rlc_ok = -1 /* the key's check for the block equation (rlc_key_ok): -1 not made yet */; };
+  std::shared_ptr<BlockVerifier> block; int rlc_ok = -1 /* the key's check for the block equation (rlc_key_ok): -1 not made yet */;
+  uint8_t tag[32] = {0} /* SHA-256 of the bytes `vk` was parsed from: the proof cache's name for this key */; };
 std::mutex g_cache_mutex; std::map<std::string, ProverSlot> g_provers; std::map<std::string, VkSlot> g_vks;
 
 std::unique_ptr<Circuit> make_circuit(CircuitKind k, bool emit, size_t depth = 8) {
@@ -186,10 +188,15 @@ HeldUnit acquire_prover(CircuitKind k, size_t depth = 8) {
   for (const auto &u : *list) { std::unique_lock<std::mutex> lk(u->busy, std::try_to_lock); if (lk.owns_lock()) return HeldUnit{u, std::move(lk)}; }
   const std::shared_ptr<ProverUnit> &u = (*list)[(turn / (unsigned)D) % list->size()]; return HeldUnit{u, std::unique_lock<std::mutex>(u->busy)};
 }
-std::shared_ptr<PreparedVerifyingKey> vk_for_path(const std::string &path) {
+// tag_out (may be null): the tag of the key that is returned, read under the same lock
+std::shared_ptr<PreparedVerifyingKey> vk_for_path(const std::string &path, uint8_t *tag_out = nullptr) {
   FileStamp st; if (!stamp_of(path, st)) throw std::runtime_error("verification key not found: " + path);
   std::lock_guard<std::mutex> lk(g_cache_mutex); VkSlot &slot = g_vks[path];
-  if (!slot.vk || !(slot.stamp == st)) { slot.vk = prepare_verifying_key(load_verifying_key(path)); slot.gpu.reset(); slot.block.reset(); slot.rlc_ok = -1; slot.stamp = st; }
+  if (!slot.vk || !(slot.stamp == st)) {
+    std::vector<uint8_t> bytes; std::shared_ptr<PreparedVerifyingKey> vk = prepare_verifying_key(load_verifying_key(path, &bytes));
+    sha256(bytes.data(), bytes.size(), slot.tag); slot.vk = vk; slot.gpu.reset(); slot.block.reset(); slot.rlc_ok = -1; slot.stamp = st;
+  }
+  if (tag_out) memcpy(tag_out, slot.tag, 32);
   return slot.vk;
 }
 std::shared_ptr<PreparedVerifyingKey> vk_for(CircuitKind k) { return vk_for_path(key_path(k, false)); }
@@ -481,6 +488,17 @@ template <class Fn> static int guarded_snset(zkgpu_snset *s, Fn fn) {
 // the serial number a record spends, as the 32 bytes of its common.Hash: snold (args[3]) for deposit, args[1] for mint, send and redeem; the set's key is what
 // common.BytesToAddress keeps of it, bytes 12..31
 static const uint8_t *record_sn(const zk_block_record &r) { return r.kind == ZK_KIND_DEPOSIT ? r.args[3] : r.args[1]; }
+// the proof cache's handle: it locks for itself (its own mutex, then a set's, then the device mutex: gpu_proof_cache.hip)
+struct zkgpu_proof_cache { ProofCache c; zkgpu_proof_cache(uint64_t capacity, const uint8_t *salt) : c(capacity, salt) {} };
+template <class Fn> static int guarded_cache(zkgpu_proof_cache *c, Fn fn) {
+  try {
+    if (!gpu_available()) { zkgpu_set_error("no HIP device visible; libzkgpu has no CPU fallback"); return ZKGPU_ERR_NO_DEVICE; }
+    if (!c) { zkgpu_set_error("no proof cache"); return ZKGPU_ERR_ARG; }
+    return fn();
+  }
+  catch (const std::exception &e) { zkgpu_set_error(e.what()); return ZKGPU_ERR_RUNTIME; }
+  catch (...) { zkgpu_set_error("unknown error"); return ZKGPU_ERR_RUNTIME; }
+}
 static void sn_keys(const uint8_t *sns, size_t n, std::vector<uint8_t> &keys) { keys.resize(20 * n); for (size_t i = 0; i < n; i++) memcpy(&keys[20 * i], sns + 32 * i + 12, 20); }
 
 extern "C" {
@@ -1286,6 +1304,79 @@ static int verify_block_records(const zk_block_record *recs, int n, unsigned cha
   }
   catch (...) { for (int i = 0; i < n; i++) ok[i] = 0; return -1; }
 }
+
+// ---- the proof cache in front of the proof step (DESIGN.md "Proof cache"; include/zk_proof_cache.h) ---------------------------------------------------------
+// The key of a record: the first 20 bytes of SHA-256(salt || vktag || record).  record_digests makes the keys of a call, on the device (k_record_digest) or by the
+// host model below, which is the same function on notes.cpp's SHA-256; a record whose kind has no bit in `kinds` gets 20 zero bytes.
+// Below this many records the host model is used even where a device is there: it costs the host 2.1 us a record, the device road 0.07-0.10 ms for its upload,
+// launch and download up to a few hundred records (profiles/proof_cache.txt): the two meet between 32 and 64 records.
+static const size_t DIGEST_DEVICE_MIN = 48;
+static void record_digests(const uint8_t salt[32], const uint8_t (*tags)[32], uint32_t kinds, const zk_block_record *recs, size_t n, bool device, uint8_t *out20) {
+  if (device) {
+    uint32_t mid[32]; memset(mid, 0, sizeof mid);                                        // the state after the block salt || vktag, once per kind and call
+    for (int k = 0; k < 4; k++) if ((kinds >> k) & 1u) { uint8_t st[32]; sha256_compress_raw(salt, tags[k], st);
+      for (int j = 0; j < 8; j++) mid[8 * k + j] = (uint32_t)st[4 * j] << 24 | (uint32_t)st[4 * j + 1] << 16 | (uint32_t)st[4 * j + 2] << 8 | st[4 * j + 3]; }
+    std::lock_guard<std::mutex> gl(g_gpu_mutex); record_digests_dev((const uint8_t *)recs, n, mid, kinds, out20); return;
+  }
+  uint8_t m[64 + sizeof(zk_block_record)], d[32]; memcpy(m, salt, 32);
+  for (size_t i = 0; i < n; i++) {
+    const uint8_t kind = recs[i].kind; if (kind > 3 || !((kinds >> kind) & 1u)) { memset(out20 + 20 * i, 0, 20); continue; }
+    memcpy(m + 32, tags[kind], 32); memcpy(m + 64, &recs[i], sizeof(zk_block_record)); sha256(m, sizeof m, d); memcpy(out20 + 20 * i, d, 20);
+  }
+}
+// verify_block_records behind an optional cache: the keys, the lookup, the misses in one contiguous array through verify_block_records unchanged, the verdicts
+// scattered back with ok = 1 for the hits, and the accepted misses stored.  Lookup and insert are two critical sections of the cache; verification between them runs
+// without its mutex, so two threads may both verify a record — it is then stored once.  The cache never costs a decision: if a step of it throws, every record is
+// treated as a miss and nothing is stored, which is the uncached entry.  A kind's tag is read before verification and again after it, and its records are stored only
+// if the two are equal: a key file replaced during the call stores nothing under either name.
+static int verify_block_records_cached(zkgpu_proof_cache *cache, const zk_block_record *recs, int n, unsigned char *ok, const char *who) {
+  if (!cache || n <= 0 || !gpu_available()) return verify_block_records(recs, n, ok, who);
+  const size_t N = (size_t)n; std::vector<uint8_t> keys, has_key, hit; uint8_t tags[4][32]; uint32_t kinds = 0; bool usable = false; size_t n_hit = 0;
+  try {
+    has_key.assign(N, 0); hit.assign(N, 0); bool present[4] = {false, false, false, false};
+    for (size_t i = 0; i < N; i++) if (recs[i].kind <= 3) present[recs[i].kind] = true;
+    for (int k = 0; k < 4; k++) if (present[k]) {                                         // (a kind whose key cannot be loaded has no key: its records go to verification as they are)
+      try { vk_for_path(key_path((CircuitKind)k, false), tags[k]); kinds |= 1u << k; } catch (const std::exception &) {} }
+    if (kinds) {
+      HostSpan span("host.cache_lookup");
+      keys.resize(20 * N); record_digests(cache->c.salt(), tags, kinds, recs, N, N >= DIGEST_DEVICE_MIN, keys.data());
+      std::vector<uint8_t> packed; std::vector<size_t> at; packed.reserve(20 * N); at.reserve(N);
+      for (size_t i = 0; i < N; i++) if (recs[i].kind <= 3 && ((kinds >> recs[i].kind) & 1u)) { has_key[i] = 1; at.push_back(i); packed.insert(packed.end(), &keys[20 * i], &keys[20 * i] + 20); }
+      std::vector<uint8_t> h(at.size(), 0); cache->c.lookup(packed.data(), at.size(), h.data());
+      for (size_t j = 0; j < at.size(); j++) { hit[at[j]] = h[j]; n_hit += h[j] != 0; }
+      usable = true;
+    }
+  }
+  catch (const std::exception &e) { fprintf(stderr, "libzkgpu: %s: the proof cache failed (%s); verifying every record\n", who, e.what()); usable = false; n_hit = 0; }
+  catch (...) { fprintf(stderr, "libzkgpu: %s: the proof cache failed; verifying every record\n", who); usable = false; n_hit = 0; }
+  int rc;
+  if (!n_hit) rc = verify_block_records(recs, n, ok, who);
+  else {
+    try {
+      std::vector<zk_block_record> miss; std::vector<size_t> idx; miss.reserve(N - n_hit); idx.reserve(N - n_hit);
+      { HostSpan span("host.cache_gather"); for (size_t i = 0; i < N; i++) if (!hit[i]) { miss.push_back(recs[i]); idx.push_back(i); } }
+      std::vector<unsigned char> mok(miss.size() + 1, 0);
+      rc = miss.empty() ? 0 : verify_block_records(miss.data(), (int)miss.size(), mok.data(), who);   // (a block of hits alone runs no verifier at all)
+      if (rc < 0) { for (int i = 0; i < n; i++) ok[i] = 0; return -1; }
+      for (size_t i = 0; i < N; i++) ok[i] = hit[i] ? 1 : 0;
+      for (size_t j = 0; j < idx.size(); j++) ok[idx[j]] = mok[j];
+      rc += (int)n_hit;
+    }
+    catch (const std::exception &e) { fprintf(stderr, "libzkgpu: %s: the proof cache failed (%s); verifying every record\n", who, e.what()); return verify_block_records(recs, n, ok, who); }
+  }
+  if (rc < 0 || !usable) return rc;
+  try {
+    bool same[4] = {false, false, false, false};
+    for (int k = 0; k < 4; k++) if ((kinds >> k) & 1u) { uint8_t t[32];
+      try { vk_for_path(key_path((CircuitKind)k, false), t); same[k] = !memcmp(t, tags[k], 32); } catch (const std::exception &) {} }
+    std::vector<uint8_t> mask(N, 0); bool any = false;
+    for (size_t i = 0; i < N; i++) { mask[i] = has_key[i] && !hit[i] && ok[i] && same[recs[i].kind]; any |= mask[i] != 0; }
+    if (any) { HostSpan span("host.cache_insert"); cache->c.insert(keys.data(), mask.data(), N); }
+  }
+  catch (const std::exception &e) { fprintf(stderr, "libzkgpu: %s: the proof cache stored nothing (%s)\n", who, e.what()); }
+  catch (...) { fprintf(stderr, "libzkgpu: %s: the proof cache stored nothing\n", who); }
+  return rc;
+}
 }  // namespace
 
 int verifyBlockRecords(const zk_block_record *recs, int n, unsigned char *ok) {
@@ -1539,7 +1630,8 @@ int genRoots(const zk_cmt_lists *l, int depth, uint8_t *roots) {
 }
 // verifyBlockRecords, then RT of every record that names a list against that list's depth-8 root.  The roots of all lists are made once, on the device; a list of
 // more than 256 commitments has no depth-8 root: it is computed as an empty one and rejects whoever names it.
-int verifyBlockRecordsRoots(const zk_block_record *recs, int n, const zk_cmt_lists *l, const int32_t *list_of, unsigned char *ok) {
+// (cache: the proof step goes through verify_block_records_cached; null = no cache, the entry as it always was)
+static int block_records_roots(const zk_block_record *recs, int n, const zk_cmt_lists *l, const int32_t *list_of, unsigned char *ok, zkgpu_proof_cache *cache = nullptr) {
   if (n < 0 || (n && (!recs || !ok))) return -1;
   auto fail = [&](const std::string &why) { zkgpu_set_error(why); fprintf(stderr, "libzkgpu: verifyBlockRecordsRoots: %s\n", why.c_str()); for (int i = 0; i < n; i++) ok[i] = 0; return -1; };
   try {
@@ -1563,7 +1655,7 @@ int verifyBlockRecordsRoots(const zk_block_record *recs, int n, const zk_cmt_lis
         if (!done) list_roots_host(8, l->cmts, ranges.data(), n_lists, true, roots.data());
       }
     }
-    const int rc = verify_block_records(recs, n, ok, "verifyBlockRecordsRoots"); if (rc < 0 || !list_of) return rc;
+    const int rc = verify_block_records_cached(cache, recs, n, ok, "verifyBlockRecordsRoots"); if (rc < 0 || !list_of) return rc;
     HostSpan span("host.roots_compare"); int accepted = 0;
     for (int i = 0; i < n; i++) {
       const int32_t j = list_of[i];
@@ -1575,6 +1667,7 @@ int verifyBlockRecordsRoots(const zk_block_record *recs, int n, const zk_cmt_lis
   catch (const std::exception &e) { return fail(e.what()); }
   catch (...) { return fail("unknown error"); }
 }
+int verifyBlockRecordsRoots(const zk_block_record *recs, int n, const zk_cmt_lists *l, const int32_t *list_of, unsigned char *ok) { return block_records_roots(recs, n, l, list_of, ok); }
 
 // ---- the resident set of spent serial numbers (DESIGN.md "Spent serial numbers"; include/zkgpu.h, include/zk_spent.h) ----------------------------------------
 static zkgpu_snset *snset_create(const uint8_t *exempt, int log2_slots, const uint64_t *seed) {
@@ -1658,8 +1751,9 @@ long long zkSnSetSpend(zk_snset *set, const uint8_t *sns, int n, int commit, uns
   if (rc != ZKGPU_OK) { fprintf(stderr, "libzkgpu: zkSnSetSpend: %s\n", zkgpu_last_error()); return -1; }
   return (long long)size;
 }
-int verifyBlockFull(const zk_block_record *recs, int n, const zk_cmt_lists *l, const int32_t *list_of, zk_snset *set, int commit, unsigned char *ok, long long *size_out) {
-  const int accepted = verifyBlockRecordsRoots(recs, n, l, list_of, ok); if (accepted < 0 || !set) return accepted;
+static int block_full(const zk_block_record *recs, int n, const zk_cmt_lists *l, const int32_t *list_of, zk_snset *set, int commit, unsigned char *ok, long long *size_out,
+                      zkgpu_proof_cache *cache = nullptr) {
+  const int accepted = block_records_roots(recs, n, l, list_of, ok, cache); if (accepted < 0 || !set) return accepted;
   uint64_t size = 0; std::vector<uint8_t> conflict;
   const int rc = guarded_snset(set, [&] {
     std::vector<uint8_t> keys((size_t)20 * n); conflict.resize((size_t)n);
@@ -1671,6 +1765,44 @@ int verifyBlockFull(const zk_block_record *recs, int n, const zk_cmt_lists *l, c
   if (size_out) *size_out = (long long)size;
   return still;
 }
+int verifyBlockFull(const zk_block_record *recs, int n, const zk_cmt_lists *l, const int32_t *list_of, zk_snset *set, int commit, unsigned char *ok, long long *size_out) {
+  return block_full(recs, n, l, list_of, set, commit, ok, size_out); }
+
+// ---- the proof cache (DESIGN.md "Proof cache"; include/zkgpu.h, include/zk_proof_cache.h) ----------------------------------------------------------------------
+static zkgpu_proof_cache *proof_cache_create(uint64_t capacity, const uint8_t *salt) {
+  zkgpu_proof_cache *c = nullptr;
+  try {
+    if (!gpu_available()) { zkgpu_set_error("no HIP device visible; libzkgpu has no CPU fallback"); return nullptr; }
+    if (capacity < 2) { zkgpu_set_error("proof cache: a capacity of 2 entries or more"); return nullptr; }
+    c = new zkgpu_proof_cache(capacity, salt);
+  }
+  catch (const std::exception &e) { zkgpu_set_error(e.what()); } catch (...) { zkgpu_set_error("unknown error"); }
+  return c;
+}
+zkgpu_proof_cache *zkgpu_proof_cache_create(uint64_t capacity) { return proof_cache_create(capacity, nullptr); }
+zkgpu_proof_cache *zkgpu_test_proof_cache_create(uint64_t capacity, const uint8_t salt[32]) {
+  if (!salt) { zkgpu_set_error("proof cache: no salt"); return nullptr; }
+  return proof_cache_create(capacity, salt); }
+void zkgpu_proof_cache_destroy(zkgpu_proof_cache *c) { try { delete c; } catch (...) {} }
+int zkgpu_proof_cache_clear(zkgpu_proof_cache *c) { return guarded_cache(c, [&] { c->c.clear(); return ZKGPU_OK; }); }
+int zkgpu_proof_cache_stats(zkgpu_proof_cache *c, uint64_t out[4]) { return guarded_cache(c, [&] { if (!out) return ZKGPU_ERR_ARG; c->c.stats(out); return ZKGPU_OK; }); }
+int zkgpu_test_record_digests(const uint8_t salt[32], const uint8_t tags[4][32], const zk_block_record *recs, size_t n, int device, uint8_t *out20) { return guarded_host([&] {
+  if (!salt || !tags || (n && (!recs || !out20))) { zkgpu_set_error("record digests: a null pointer"); return ZKGPU_ERR_ARG; }
+  if (device && !gpu_available()) { zkgpu_set_error("no HIP device visible; libzkgpu has no CPU fallback"); return ZKGPU_ERR_NO_DEVICE; }
+  record_digests(salt, tags, 0xfu, recs, n, device != 0, out20); return ZKGPU_OK; }); }
+int zkgpu_test_proof_cache_launches(uint64_t *launches) { if (!launches) return ZKGPU_ERR_ARG; *launches = record_digest_launches(); return ZKGPU_OK; }
+
+zk_proof_cache *zkProofCacheNew(long long capacity) { return capacity < 2 ? nullptr : zkgpu_proof_cache_create((uint64_t)capacity); }
+void zkProofCacheFree(zk_proof_cache *cache) { zkgpu_proof_cache_destroy(cache); }
+int zkProofCacheClear(zk_proof_cache *cache) {
+  if (zkgpu_proof_cache_clear(cache) == ZKGPU_OK) return 0;
+  fprintf(stderr, "libzkgpu: zkProofCacheClear: %s\n", zkgpu_last_error()); return -1; }
+int zkProofCacheStats(zk_proof_cache *cache, uint64_t out[4]) { return zkgpu_proof_cache_stats(cache, out) == ZKGPU_OK ? 0 : -1; }
+int verifyRecordsCached(zk_proof_cache *cache, const zk_block_record *recs, int n, unsigned char *ok) {
+  if (n < 0 || (n && (!recs || !ok))) return -1;
+  return verify_block_records_cached(cache, recs, n, ok, "verifyRecordsCached"); }
+int verifyBlockFullCached(zk_proof_cache *cache, const zk_block_record *recs, int n, const zk_cmt_lists *l, const int32_t *list_of, zk_snset *set, int commit, unsigned char *ok,
+                          long long *size_out) { return block_full(recs, n, l, list_of, set, commit, ok, size_out, cache); }
 
 // the reference's symbol names, exported by libzkgpu.so itself (the four libzk_*.so forward to the zkgpu_abi_* names above)
 char *genCMT(uint64_t v, char *a, char *b) { return zkgpu_abi_genCMT(v, a, b); }

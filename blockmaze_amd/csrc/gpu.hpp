@@ -218,6 +218,28 @@ class SpentSet {
   struct Impl; std::unique_ptr<Impl> impl;
 };
 
+// The proof cache (gpu_proof_cache.hip; DESIGN.md "Proof cache").  The key of a record is the first 20 bytes of SHA-256(salt[32] || vktag[32] || record[720]).
+// record_digests_dev: the keys of n records on the device (k_record_digest).  mid: the SHA-256 states after the block salt || vktag, eight words for each of the kinds
+// 0..3; kinds: bit k set = kind k has a key; a record of any other kind gets 20 zero bytes.  The caller holds the device mutex; runs on the main stream and returns
+// after it has been synchronised.  One process-wide workspace, kept and grown.
+void record_digests_dev(const uint8_t *recs, size_t n, const uint32_t mid[32], uint32_t kinds, uint8_t *out20);
+uint64_t record_digest_launches();   // digest kernels launched so far, process-wide (tests: a small call takes the host model)
+// The cache itself: two generations of keys, `young` and `old`, each a SpentSet without an exempt key.  One mutex per cache, taken before a set's mutex and the device
+// mutex; lookup and insert are one critical section each, and the caller verifies between them without the cache's mutex.  Every entry throws GpuError on failure.
+class ProofCache {
+ public:
+  explicit ProofCache(uint64_t capacity /* entries, 2 or more */, const uint8_t *salt = nullptr /* 32 bytes (tests); null = getrandom */);
+  ~ProofCache();
+  const uint8_t *salt() const;
+  void lookup(const uint8_t *keys, size_t q, uint8_t *hit);   // hit[i] = 1 if key i (q x 20 bytes) is in either generation as it is now; a hit in `old` is not refreshed
+  // young.spend(keys, mask, commit) over n x 20 bytes.  Before it: more than capacity / 2 masked-in records are cut to the first capacity / 2 in record order, and
+  // if young would then grow past capacity / 2, old is dropped, young becomes old and a fresh set becomes young.  The two never hold more than `capacity` keys.
+  void insert(const uint8_t *keys, const uint8_t *mask, size_t n);
+  void clear();                                                // both generations empty; the counters go on
+  void stats(uint64_t out[4]);                                 // hits, misses, keys stored, entries held now
+  struct Impl; std::unique_ptr<Impl> impl;
+};
+
 // The roots of many independent commitment lists (gpu_list_roots.hip): list i = leaves[first .. first + count) of one shared array, roots[i] = the root of the tree
 // above over that list alone (notes.cpp: merkle_root), in the caller's order.  hash_order: leaves and roots as the bytes of the common.Hash instead of blob order.
 // The caller has checked the arguments (depth 1..32, every range inside the array, count <= 2^depth) and holds the device mutex; runs on the main stream and

@@ -29,7 +29,7 @@ struct Proof { G1AffineRaw A; G2AffineRaw B; G1AffineRaw C; };   // affine, Mont
 
 // ---- the reference's on-disk format (hybrid binary/decimal) ---------------------------------------------
 ProvingKeyHost load_proving_key(const std::string &path);       // point decompression runs on the GPU
-VerifyingKeyHost load_verifying_key(const std::string &path);   // host only
+VerifyingKeyHost load_verifying_key(const std::string &path, std::vector<uint8_t> *file_bytes = nullptr);   // host only; file_bytes: receives the bytes that were parsed
 void save_proving_key(const std::string &path, const ProvingKeyHost &pk);
 void save_verifying_key(const std::string &path, const VerifyingKeyHost &vk);
 

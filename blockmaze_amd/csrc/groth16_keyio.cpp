@@ -234,8 +234,9 @@ static G2AffineRaw decompress_host_g2(const Fe32 &x0, const Fe32 &x1, uint8_t fl
   if (!fq2_sqrt_host(y2, y)) throw std::runtime_error("verification key: G2 point not on the twist");
   if ((y.c0.from_mont().l[0] & 1) != (uint64_t)(flags & 1)) y = y.neg(); return {fe_of(x.c0), fe_of(x.c1), fe_of(y.c0), fe_of(y.c1)}; }
 
-VerifyingKeyHost load_verifying_key(const std::string &path) {   // r1cs_gg_ppzksnark.tcc:100-108, accumulation_vector.tcc:63-69
+VerifyingKeyHost load_verifying_key(const std::string &path, std::vector<uint8_t> *file_bytes) {   // r1cs_gg_ppzksnark.tcc:100-108, accumulation_vector.tcc:63-69
   std::vector<uint8_t> buf = slurp(path); Cursor c{buf.data(), buf.data() + buf.size(), "verification key"}; VerifyingKeyHost vk;
+  if (file_bytes) *file_bytes = buf;
   HFq *gt = reinterpret_cast<HFq *>(&vk.alpha_g1_beta_g2); for (int i = 0; i < 12; i++) { Fe32 v; c.dec(v.l); gt[i] = fq_of(v).to_mont(); } c.eat('\n');
   std::vector<Fe32> x;
   std::vector<uint8_t> f;

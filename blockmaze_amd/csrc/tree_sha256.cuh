@@ -45,5 +45,21 @@ __device__ __forceinline__ Node tree_compress(const Node &l, const Node &r) {
   }
   return {{a + H0, b + H1, c + H2, d + H3, e + H4, f + H5, g + H6, h + H7}};
 }
+// The chained form (gpu_proof_cache.hip: a message of many blocks): one compression of the sixteen words w from the state s, which becomes the next state.  w is the
+// rolling window and is used up.
+__device__ __forceinline__ void tree_compress_chain(uint32_t s[8], uint32_t w[16]) {
+  uint32_t a = s[0], b = s[1], c = s[2], d = s[3], e = s[4], f = s[5], g = s[6], h = s[7];
+#pragma unroll
+  for (int i = 0; i < 64; i++) {
+    if (i >= 16) {
+      const uint32_t w15 = w[(i + 1) & 15], w2 = w[(i + 14) & 15];
+      w[i & 15] += (tree_rotr(w15, 7) ^ tree_rotr(w15, 18) ^ (w15 >> 3)) + w[(i + 9) & 15] + (tree_rotr(w2, 17) ^ tree_rotr(w2, 19) ^ (w2 >> 10));
+    }
+    const uint32_t t1 = h + (tree_rotr(e, 6) ^ tree_rotr(e, 11) ^ tree_rotr(e, 25)) + (g ^ (e & (f ^ g))) + TREE_K256[i] + w[i & 15];
+    const uint32_t t2 = (tree_rotr(a, 2) ^ tree_rotr(a, 13) ^ tree_rotr(a, 22)) + ((a & b) | (c & (a | b)));
+    h = g; g = f; f = e; e = d + t1; d = c; c = b; b = a; a = t1 + t2;
+  }
+  s[0] += a; s[1] += b; s[2] += c; s[3] += d; s[4] += e; s[5] += f; s[6] += g; s[7] += h;
+}
 
 }  // namespace zk

@@ -404,6 +404,32 @@ def record_sn(rec):
     """the serial number a record (RECORD_DTYPE) spends, the 32 bytes of its common.Hash: snold = args[3] for deposit, args[1] for mint, send and redeem; the set's key is [12:]"""
     return bytes(rec["args"][3 if int(rec["kind"]) == KIND["deposit"] else 1])
 
+# ---- the proof cache (include/zkgpu.h "the proof cache"; the drop-in level is include/zk_proof_cache.h) ----
+class ProofCache:
+    """the records whose proof this process has accepted, by keyed digest, in two generations on the device.  salt: the test entry (32 given bytes instead of getrandom)"""
+    def __init__(self, capacity, salt=None):
+        L = lib(); L.zkgpu_proof_cache_create.restype = ctypes.c_void_p; L.zkgpu_test_proof_cache_create.restype = ctypes.c_void_p
+        self.h = L.zkgpu_proof_cache_create(ctypes.c_uint64(capacity)) if salt is None else L.zkgpu_test_proof_cache_create(ctypes.c_uint64(capacity), bytes(salt))
+        if not self.h: raise ZkGpuError(lib().zkgpu_last_error().decode())
+    def stats(self):
+        """-> (hits, misses, keys stored, entries held now)"""
+        out = (ctypes.c_uint64 * 4)(); _check(lib().zkgpu_proof_cache_stats(ctypes.c_void_p(self.h), out)); return tuple(int(x) for x in out)
+    def clear(self): _check(lib().zkgpu_proof_cache_clear(ctypes.c_void_p(self.h)))
+    def close(self):
+        if self.h: lib().zkgpu_proof_cache_destroy(ctypes.c_void_p(self.h)); self.h = None
+    def __del__(self):
+        try: self.close()
+        except Exception: pass
+def record_digests(salt, tags, recs, device=True):
+    """zkgpu_test_record_digests: the cache keys of records under a 32-byte salt and the four kinds' 32-byte tags -> (n, 20) uint8, zeros for a kind above 3;
+    from k_record_digest (device=True) or from the host model (device=False: needs no device)"""
+    recs, ptr, n = _recs(recs); tb = b"".join(bytes(t) for t in tags); assert len(tb) == 128 and len(bytes(salt)) == 32; out = np.zeros((max(1, n), 20), dtype=np.uint8)
+    _check(lib().zkgpu_test_record_digests(bytes(salt), tb, ptr, ctypes.c_size_t(n), int(bool(device)), _bytes(out))); return out[:n]
+def proof_cache_launches():
+    """digest kernels launched by this process so far"""
+    k = ctypes.c_uint64(0); _check(lib().zkgpu_test_proof_cache_launches(ctypes.byref(k))); return int(k.value)
+def _cache_handle(cache): return None if cache is None else ctypes.c_void_p(cache.h if isinstance(cache, ProofCache) else cache)
+
 # ---- the roots of many commitment lists (include/zkgpu.h "the roots of many commitment lists"; the drop-in level is include/zk_roots.h) ----
 def _leaf_array(leaves):
     """leaves: an (n, 32) uint8 array, one bytes object of n x 32 bytes, or a list of 32-byte strings -> flat uint8 array"""
@@ -511,6 +537,26 @@ class Zk:
         l, keep = _cmt_lists(cmts, lists) if lists is not None else (None, None); lo = np.ascontiguousarray(list_of, dtype=np.int32) if list_of is not None else None; assert lo is None or lo.shape == (n,)
         ok = (ctypes.c_ubyte * max(1, n))(); size = ctypes.c_longlong(-7); self.L.verifyBlockFull.restype = ctypes.c_int
         rc = self.L.verifyBlockFull(ptr, n, ctypes.byref(l) if l is not None else None, lo.ctypes.data_as(ctypes.c_void_p) if lo is not None and n else None, ctypes.c_void_p(s) if s else None, int(bool(commit)), ok, ctypes.byref(size))
+        return rc, [bool(ok[i]) for i in range(n)], (None if size.value == -7 else int(size.value))
+    # include/zk_proof_cache.h: the proofs the pool has verified are not verified again with their block.  cache: a ProofCache, a handle of ProofCacheNew, or None
+    def ProofCacheNew(self, capacity):
+        self.L.zkProofCacheNew.restype = ctypes.c_void_p; return self.L.zkProofCacheNew(ctypes.c_longlong(capacity))   # None on failure
+    def ProofCacheFree(self, c): self.L.zkProofCacheFree(_cache_handle(c))
+    def ProofCacheClear(self, c): return int(self.L.zkProofCacheClear(_cache_handle(c)))
+    def ProofCacheStats(self, c):
+        """-> (hits, misses, records stored, entries held now), None on failure"""
+        out = (ctypes.c_uint64 * 4)(); return tuple(int(x) for x in out) if self.L.zkProofCacheStats(_cache_handle(c), out) == 0 else None
+    def VerifyRecordsCached(self, cache, items):
+        """VerifyBlockRecords with the proof step behind the cache -> (accepted, [bool])"""
+        recs = items if isinstance(items, np.ndarray) else records_from_items(items); recs, ptr, n = _recs(recs)
+        ok = (ctypes.c_ubyte * max(1, n))(); self.L.verifyRecordsCached.restype = ctypes.c_int; rc = self.L.verifyRecordsCached(_cache_handle(cache), ptr, n, ok); return rc, [bool(ok[i]) for i in range(n)]
+    def VerifyBlockFullCached(self, cache, items, cmts, lists, list_of, s, commit):
+        """VerifyBlockFull with the proof step behind the cache -> (accepted, [bool], size after or None)"""
+        recs = items if isinstance(items, np.ndarray) else records_from_items(items); recs, ptr, n = _recs(recs)
+        l, keep = _cmt_lists(cmts, lists) if lists is not None else (None, None); lo = np.ascontiguousarray(list_of, dtype=np.int32) if list_of is not None else None; assert lo is None or lo.shape == (n,)
+        ok = (ctypes.c_ubyte * max(1, n))(); size = ctypes.c_longlong(-7); self.L.verifyBlockFullCached.restype = ctypes.c_int
+        rc = self.L.verifyBlockFullCached(_cache_handle(cache), ptr, n, ctypes.byref(l) if l is not None else None, lo.ctypes.data_as(ctypes.c_void_p) if lo is not None and n else None, ctypes.c_void_p(s) if s else None,
+                                          int(bool(commit)), ok, ctypes.byref(size))
         return rc, [bool(ok[i]) for i in range(n)], (None if size.value == -7 else int(size.value))
     def GenRedeemProof(self, value, value_old, sn_old, r_old, sn, r, cmtA_old, cmtA, value_s, sk):
         return self.L.genRedeemproof(ctypes.c_uint64(value), ctypes.c_uint64(value_old), self.hx(sn_old), self.hx(r_old), self.hx(sn), self.hx(r), self.hx(cmtA_old), self.hx(cmtA), ctypes.c_uint64(value_s), self.hx(sk)).decode()

@@ -263,6 +263,24 @@ int zkgpu_test_snset_launches(uint64_t *launches);
 int zkgpu_test_snset_host(const uint8_t *resident, size_t n_resident, const uint8_t exempt[20], const uint8_t *keys, const uint8_t *mask, size_t n, int commit,
                           uint8_t *conflict, uint8_t *appended, size_t *n_appended);
 
+/* ---- the proof cache (DESIGN.md "Proof cache"; the drop-in level is zk_proof_cache.h) --------------------------------------------------------------------
+ * The records whose proof this process has accepted, by key: the first 20 bytes of SHA-256(salt[32] || vktag[32] || record[720]) — salt from getrandom at creation,
+ * vktag the SHA-256 of the bytes of the verifying-key file of the record's kind as it was loaded; every byte of the record counts.  Two generations of capacity / 2
+ * keys, each a spent set as above without an exempt key: an insert that would take the young one past capacity / 2 drops the old one first, and a call with more
+ * than capacity / 2 new records stores the first capacity / 2 in record order.  stats: out = {hits, misses, keys stored, entries held now}; clear empties both
+ * generations and leaves the three counters.  Entries of one cache may be called from any thread.  There is no host cache. */
+typedef struct zkgpu_proof_cache zkgpu_proof_cache;
+zkgpu_proof_cache *zkgpu_proof_cache_create(uint64_t capacity /* entries, 2 or more */);   /* NULL + zkgpu_last_error() on failure */
+void zkgpu_proof_cache_destroy(zkgpu_proof_cache *c);
+int zkgpu_proof_cache_clear(zkgpu_proof_cache *c);
+int zkgpu_proof_cache_stats(zkgpu_proof_cache *c, uint64_t out[4]);
+/* test entries: a cache with a given salt; the keys of n records under a salt and the four kinds' tags — out20: n x 20 bytes, 20 zero bytes for a kind above 3 —
+ * from the kernel k_record_digest whatever the count (device = 1) or from the host model on the library's own SHA-256 (device = 0: needs no device); the
+ * process-wide number of digest-kernel launches so far */
+zkgpu_proof_cache *zkgpu_test_proof_cache_create(uint64_t capacity, const uint8_t salt[32]);
+int zkgpu_test_record_digests(const uint8_t salt[32], const uint8_t tags[4][32], const zk_block_record *recs, size_t n, int device, uint8_t *out20);
+int zkgpu_test_proof_cache_launches(uint64_t *launches);
+
 #ifdef __cplusplus
 }
 #endif
