@@ -36,6 +36,7 @@
 #include "../../include/zk_roots.h"
 #include "../../include/zk_spent.h"
 #include "../../include/zk_proof_cache.h"
+#include "../../include/zk_spent_pk.h"
 #include "../../include/zkgpu.h"
 #include "blockmaze_circuits.hpp"
 #include "groth16.hpp"
@@ -498,6 +499,18 @@ template <class Fn> static int guarded_cache(zkgpu_proof_cache *c, Fn fn) {
   }
   catch (const std::exception &e) { zkgpu_set_error(e.what()); return ZKGPU_ERR_RUNTIME; }
   catch (...) { zkgpu_set_error("unknown error"); return ZKGPU_ERR_RUNTIME; }
+}
+typedef std::array<uint8_t, 20> SnKey20;
+static SnKey20 sn_key20(const uint8_t *p) { SnKey20 k; memcpy(k.data(), p, 20); return k; }
+void zk::snset_pairs_finish_host(const uint8_t *keys, const uint8_t *active, size_t n, uint8_t *status, uint8_t *code) {
+  std::set<SnKey20> taken;
+  for (size_t i = 0; i < n; i++) if (status[i] == 1) for (size_t j = 0; j < 2; j++) if (active[2 * i + j]) taken.insert(sn_key20(keys + 20 * (2 * i + j)));
+  for (size_t i = 0; i < n; i++) {
+    if (status[i] != 0) continue;
+    const bool a0 = active[2 * i] != 0, a1 = active[2 * i + 1] != 0; const SnKey20 k0 = sn_key20(keys + 40 * i), k1 = sn_key20(keys + 40 * i + 20);
+    if ((a0 && taken.count(k0)) || (a1 && taken.count(k1)) || (a0 && a1 && k0 == k1)) { status[i] = 2; code[i] = 2; continue; }
+    status[i] = 1; if (a0) taken.insert(k0); if (a1) taken.insert(k1);
+  }
 }
 static void sn_keys(const uint8_t *sns, size_t n, std::vector<uint8_t> &keys) { keys.resize(20 * n); for (size_t i = 0; i < n; i++) memcpy(&keys[20 * i], sns + 32 * i + 12, 20); }
 
@@ -1719,6 +1732,32 @@ int zkgpu_test_snset_host(const uint8_t *resident, size_t n_resident, const uint
     seen.insert(k); if (commit) memcpy(appended + 20 * added++, k.data(), 20);                    // CreateAccount
   }
   *n_appended = added; return ZKGPU_OK; }); }
+// ---- two keys a record (DESIGN.md "Two keys a record"; include/zk_spent_pk.h) -----------------------------------------------------------------------------------
+int zkgpu_snset_spend_pairs(zkgpu_snset *s, const uint8_t *keys, const uint8_t *nkeys, size_t n, int commit, uint8_t *conflict, uint64_t *size_out) { return guarded_snset(s, [&] {
+  if (!s->s.spend_pairs(keys, nkeys, n, commit != 0, conflict, size_out)) { zkgpu_set_error("spent set: a null pointer, more than two keys a record, or the log could reach 2^32 - 2 entries"); return ZKGPU_ERR_ARG; }
+  return ZKGPU_OK; }); }
+int zkgpu_test_snset_round_cap(zkgpu_snset *s, uint32_t rounds) { return guarded_snset(s, [&] { s->s.set_round_cap(rounds); return ZKGPU_OK; }); }
+int zkgpu_test_snset_rounds(uint64_t *rounds, uint64_t *host_finishes) { if (!rounds || !host_finishes) return ZKGPU_ERR_ARG; SpentSet::rounds(*rounds, *host_finishes); return ZKGPU_OK; }
+// the model: the loop above with up to two keys a record.  Exist on each key -> 1; a key that an earlier accepted record of the call created, or k1 == k2 -> 2;
+// otherwise CreateAccount on each, k1 first.  The exempt key is skipped as k1 and rejects as k2.
+int zkgpu_test_snset_host_pairs(const uint8_t *resident, size_t n_resident, const uint8_t exempt[20], const uint8_t *keys, const uint8_t *nkeys, size_t n, int commit,
+                                uint8_t *conflict, uint8_t *appended, size_t *n_appended) { return guarded_host([&] {
+  if ((n_resident && !resident) || (n && (!keys || !nkeys || !conflict || (commit && !appended))) || !n_appended) return ZKGPU_ERR_ARG;
+  for (size_t i = 0; i < n; i++) if (nkeys[i] > 2) return ZKGPU_ERR_ARG;
+  std::set<SnKey20> state, seen; for (size_t i = 0; i < n_resident; i++) state.insert(sn_key20(resident + 20 * i));
+  size_t added = 0;
+  for (size_t i = 0; i < n; i++) {
+    const uint8_t *k = keys + 40 * i; conflict[i] = 0; if (!nkeys[i]) continue;
+    SnKey20 ks[2]; size_t m = 0;
+    if (!(exempt && !memcmp(k, exempt, 20))) ks[m++] = sn_key20(k);
+    if (nkeys[i] == 2) { if (exempt && !memcmp(k + 20, exempt, 20)) { conflict[i] = 1; continue; } ks[m++] = sn_key20(k + 20); }
+    bool in_state = false, in_call = m == 2 && ks[0] == ks[1];
+    for (size_t j = 0; j < m; j++) { in_state |= state.count(ks[j]) != 0; in_call |= seen.count(ks[j]) != 0; }
+    if (in_state) { conflict[i] = 1; continue; }
+    if (in_call) { conflict[i] = 2; continue; }
+    for (size_t j = 0; j < m; j++) { seen.insert(ks[j]); if (commit) memcpy(appended + 20 * added++, ks[j].data(), 20); }
+  }
+  *n_appended = added; return ZKGPU_OK; }); }
 
 zk_snset *zkSnSetNew(const uint8_t *exempt_sn) { return zkgpu_snset_create(exempt_sn ? exempt_sn + 12 : nullptr); }
 void zkSnSetFree(zk_snset *set) { zkgpu_snset_destroy(set); }
@@ -1767,6 +1806,42 @@ static int block_full(const zk_block_record *recs, int n, const zk_cmt_lists *l,
 }
 int verifyBlockFull(const zk_block_record *recs, int n, const zk_cmt_lists *l, const int32_t *list_of, zk_snset *set, int commit, unsigned char *ok, long long *size_out) {
   return block_full(recs, n, l, list_of, set, commit, ok, size_out); }
+// include/zk_spent_pk.h: an all-zero pks[i] = record i has no second key
+long long zkSnSetSpendPairs(zk_snset *set, const uint8_t *sns, const uint8_t *pks, int n, int commit, unsigned char *spent) {
+  uint64_t size = 0;
+  const int rc = guarded_snset(set, [&] {
+    if (n < 0 || (n && (!sns || !spent))) { zkgpu_set_error("zkSnSetSpendPairs: a negative count or a null pointer"); return ZKGPU_ERR_ARG; }
+    static const uint8_t none[32] = {0};
+    std::vector<uint8_t> keys((size_t)40 * n), nkeys((size_t)n), conflict((size_t)n);
+    for (int i = 0; i < n; i++) {
+      memcpy(&keys[40 * (size_t)i], sns + 32 * (size_t)i + 12, 20); nkeys[i] = 1;
+      if (pks && memcmp(pks + 32 * (size_t)i, none, 32)) { memcpy(&keys[40 * (size_t)i + 20], pks + 32 * (size_t)i + 12, 20); nkeys[i] = 2; }
+    }
+    if (!set->s.spend_pairs(keys.data(), nkeys.data(), (size_t)n, commit != 0, conflict.data(), &size)) { zkgpu_set_error("zkSnSetSpendPairs: the log could reach 2^32 - 2 entries"); return ZKGPU_ERR_ARG; }
+    for (int i = 0; i < n; i++) spent[i] = conflict[i] != 0;
+    return ZKGPU_OK; });
+  if (rc != ZKGPU_OK) { fprintf(stderr, "libzkgpu: zkSnSetSpendPairs: %s\n", zkgpu_last_error()); return -1; }
+  return (long long)size;
+}
+// block_full with the spend step on pairs: a deposit brings its one-time pk address (args[1][0..19]) as second key
+int verifyBlockState(zk_proof_cache *cache, const zk_block_record *recs, int n, const zk_cmt_lists *l, const int32_t *list_of, zk_snset *set, int commit, unsigned char *ok,
+                     long long *size_out) {
+  const int accepted = block_records_roots(recs, n, l, list_of, ok, cache); if (accepted < 0 || !set) return accepted;
+  uint64_t size = 0; std::vector<uint8_t> conflict;
+  const int rc = guarded_snset(set, [&] {
+    std::vector<uint8_t> keys((size_t)40 * n), nkeys((size_t)n); conflict.resize((size_t)n);
+    { HostSpan span("host.sn_keys");
+      for (int i = 0; i < n; i++) {
+        uint8_t *k = &keys[40 * (size_t)i]; memcpy(k, record_sn(recs[i]) + 12, 20); nkeys[i] = !ok[i] ? 0 : recs[i].kind == ZK_KIND_DEPOSIT ? 2 : 1;
+        if (recs[i].kind == ZK_KIND_DEPOSIT) memcpy(k + 20, recs[i].args[1], 20);
+      } }
+    if (!set->s.spend_pairs(keys.data(), nkeys.data(), (size_t)n, commit != 0, conflict.data(), &size)) { zkgpu_set_error("the log could reach 2^32 - 2 entries"); return ZKGPU_ERR_ARG; }
+    return ZKGPU_OK; });
+  if (rc != ZKGPU_OK) { fprintf(stderr, "libzkgpu: verifyBlockState: %s\n", zkgpu_last_error()); for (int i = 0; i < n; i++) ok[i] = 0; return -1; }
+  int still = 0; for (int i = 0; i < n; i++) { if (conflict[i]) ok[i] = 0; still += ok[i] != 0; }
+  if (size_out) *size_out = (long long)size;
+  return still;
+}
 
 // ---- the proof cache (DESIGN.md "Proof cache"; include/zkgpu.h, include/zk_proof_cache.h) ----------------------------------------------------------------------
 static zkgpu_proof_cache *proof_cache_create(uint64_t capacity, const uint8_t *salt) {

@@ -210,6 +210,14 @@ class SpentSet {
   // fresh, 1 the key was in the set before the call, 2 an earlier masked-in record of the call has it.  commit: the fresh keys are appended in record order;
   // otherwise the set is afterwards what it was, bit for bit.  One upload, at most one rebuild, three launches and one download whatever n is.
   bool spend(const uint8_t *keys, const uint8_t *mask, size_t n, bool commit, uint8_t *conflict, uint64_t *size_out /* or null */);
+  // The same loop with up to two keys a record (keys: n x 2 x 20 bytes, k1 then k2; nkeys[i] = 0 masked out, 1 or 2; more is a bad argument).  The exempt key applies
+  // to k1 only.  conflict[i] = 1 a key of the record was in the set before the call, or k2 is the exempt key; else 2 an earlier ACCEPTED record of the call has one of
+  // its keys, or k1 == k2; else 0 accepted: with commit its keys are appended, k1 before k2.  A rejected record inserts nothing.  Decided in parallel rounds (DESIGN.md
+  // "Two keys a record"): four launches a round whatever n is, one round without conflicts inside the batch; after the round cap the host decides the live records.
+  // With commit, a slot that a rejected record held in the last round is left as a tombstone.  Needs n_old + 2n < 2^32 - 2.
+  bool spend_pairs(const uint8_t *keys, const uint8_t *nkeys, size_t n, bool commit, uint8_t *conflict, uint64_t *size_out /* or null */);
+  void set_round_cap(uint32_t rounds);                                        // tests: the round cap of this set; 0 = the default
+  static void rounds(uint64_t &rounds, uint64_t &host_finishes);              // rounds run and host finishes made by all sets of the process so far (tests)
   bool query(uint64_t size, const uint8_t *keys, size_t q, uint64_t *index, bool current = false);   // index[i] = the key's position in the log if below `size` (current: below size()), else 2^64 - 1
   bool rewind(uint64_t size);                                                 // the set becomes state `size`
   bool read_log(uint64_t first, uint64_t count, uint8_t *out);                // keys first .. first + count - 1 of the log, 20 bytes each
@@ -217,6 +225,11 @@ class SpentSet {
   static uint64_t launches();                                                 // kernels launched by all sets of the process so far (tests)
   struct Impl; std::unique_ptr<Impl> impl;
 };
+
+// spend_pairs after the round cap (capi_zk.cpp: host code, so the sanitizer builds cover it): the sequential loop on what the rounds left.  keys: n x 2 x 20 bytes,
+// active: 2n flags.  The keys of the accepted records go into a host set; the live records (status 0) are walked in order and become accepted (1), or rejected (2)
+// with code 2 where a key is in that set or k1 == k2.  No live record has a resident key: the first round rejected those.
+void snset_pairs_finish_host(const uint8_t *keys, const uint8_t *active, size_t n, uint8_t *status, uint8_t *code);
 
 // The proof cache (gpu_proof_cache.hip; DESIGN.md "Proof cache").  The key of a record is the first 20 bytes of SHA-256(salt[32] || vktag[32] || record[720]).
 // record_digests_dev: the keys of n records on the device (k_record_digest).  mid: the SHA-256 states after the block salt || vktag, eight words for each of the kinds

@@ -367,6 +367,12 @@ class SpentSet:
         buf, n = _keys20(keys); m = bytes(bytearray(int(bool(x)) for x in mask)) if mask is not None else None; assert m is None or len(m) == n
         out = ctypes.create_string_buffer(max(1, n)); size = ctypes.c_uint64(0)
         _check(lib().zkgpu_snset_spend(ctypes.c_void_p(self.h), buf, m, ctypes.c_size_t(n), int(bool(commit)), out, ctypes.byref(size))); return list(out.raw[:n]), int(size.value)
+    def spend_pairs(self, pairs, commit=True):
+        """pairs: one entry a record — None or () (masked out), (k1,) or (k1, k2), 20-byte keys -> ([code per record: 0 accepted or masked out, 1 a key was in the set before
+        the call or k2 is the exempt key, 2 an earlier accepted record of the call has one of the keys or k1 == k2], the size after the call)"""
+        buf, nk, n = _pairs40(pairs); out = ctypes.create_string_buffer(max(1, n)); size = ctypes.c_uint64(0)
+        _check(lib().zkgpu_snset_spend_pairs(ctypes.c_void_p(self.h), buf, nk, ctypes.c_size_t(n), int(bool(commit)), out, ctypes.byref(size))); return list(out.raw[:n]), int(size.value)
+    def round_cap(self, rounds): _check(lib().zkgpu_test_snset_round_cap(ctypes.c_void_p(self.h), ctypes.c_uint32(rounds)))   # test entry: 0 = the default
     def query(self, size, keys):
         """-> [position of the key in the log if it is below `size`, else None]"""
         buf, q = _keys20(keys); out = (ctypes.c_uint64 * max(1, q))()
@@ -386,6 +392,12 @@ class SpentSet:
     def __del__(self):
         try: self.close()
         except Exception: pass
+def _pairs40(pairs):
+    """[None | (k1,) | (k1, k2)] -> (n x 40 bytes, n bytes of key counts, n)"""
+    buf = bytearray(); nk = bytearray()
+    for p in pairs:
+        p = tuple(p or ()); assert len(p) <= 2 and all(len(k) == 20 for k in p); nk.append(len(p)); buf += b"".join(bytes(k) for k in p) + bytes(20 * (2 - len(p)))
+    return bytes(buf), bytes(nk), len(nk)
 def snset_launches():
     """kernels launched by all spent sets of this process so far"""
     k = ctypes.c_uint64(0); _check(lib().zkgpu_test_snset_launches(ctypes.byref(k))); return int(k.value)
@@ -395,6 +407,15 @@ def snset_host(resident, exempt, keys, mask=None, commit=True):
     out = ctypes.create_string_buffer(max(1, n)); app = ctypes.create_string_buffer(max(1, 20 * n)); na = ctypes.c_size_t(0)
     _check(lib().zkgpu_test_snset_host(rb if nr else None, ctypes.c_size_t(nr), bytes(exempt) if exempt is not None else None, kb if n else None, m, ctypes.c_size_t(n), int(bool(commit)), out, app, ctypes.byref(na)))
     return list(out.raw[:n]), [app.raw[20 * i:20 * i + 20] for i in range(int(na.value))]
+def snset_host_pairs(resident, exempt, pairs, commit=True):
+    """zkgpu_test_snset_host_pairs: the sequential loop with up to two keys a record (pairs as SpentSet.spend_pairs takes them) -> ([conflict code], [appended key])"""
+    rb, nr = _keys20(resident); buf, nk, n = _pairs40(pairs); out = ctypes.create_string_buffer(max(1, n)); app = ctypes.create_string_buffer(max(1, 40 * n)); na = ctypes.c_size_t(0)
+    _check(lib().zkgpu_test_snset_host_pairs(rb if nr else None, ctypes.c_size_t(nr), bytes(exempt) if exempt is not None else None, buf if n else None, nk if n else None, ctypes.c_size_t(n), int(bool(commit)), out, app,
+                                             ctypes.byref(na)))
+    return list(out.raw[:n]), [app.raw[20 * i:20 * i + 20] for i in range(int(na.value))]
+def snset_rounds():
+    """(rounds the spent sets of this process have run on the device, calls the host finished after the round cap)"""
+    r = ctypes.c_uint64(0); h = ctypes.c_uint64(0); _check(lib().zkgpu_test_snset_rounds(ctypes.byref(r), ctypes.byref(h))); return int(r.value), int(h.value)
 def snset_home(key, seed, n_slots):
     """the documented mix (include/zkgpu.h): the home slot of a 20-byte key in a table of n_slots slots"""
     M = (1 << 64) - 1; h = seed
@@ -537,6 +558,20 @@ class Zk:
         l, keep = _cmt_lists(cmts, lists) if lists is not None else (None, None); lo = np.ascontiguousarray(list_of, dtype=np.int32) if list_of is not None else None; assert lo is None or lo.shape == (n,)
         ok = (ctypes.c_ubyte * max(1, n))(); size = ctypes.c_longlong(-7); self.L.verifyBlockFull.restype = ctypes.c_int
         rc = self.L.verifyBlockFull(ptr, n, ctypes.byref(l) if l is not None else None, lo.ctypes.data_as(ctypes.c_void_p) if lo is not None and n else None, ctypes.c_void_p(s) if s else None, int(bool(commit)), ok, ctypes.byref(size))
+        return rc, [bool(ok[i]) for i in range(n)], (None if size.value == -7 else int(size.value))
+    # include/zk_spent_pk.h: two keys a record, a deposit's one-time pk address included
+    def SnSetSpendPairs(self, s, sns, pks=None, commit=True):
+        """pks: None, or one entry a record: 32 bytes with the address at [12:], or None / 32 zero bytes = no second key -> (the size after the call or -1, [spent?])"""
+        n = len(sns); buf = b"".join(bytes(x) for x in sns); pb = b"".join(bytes(x) if x is not None else bytes(32) for x in pks) if pks is not None else None; assert pb is None or len(pb) == 32 * n
+        out = ctypes.create_string_buffer(max(1, n)); self.L.zkSnSetSpendPairs.restype = ctypes.c_longlong
+        size = int(self.L.zkSnSetSpendPairs(ctypes.c_void_p(s) if s else None, buf, pb, n, int(bool(commit)), out)); return size, [bool(b) for b in out.raw[:n]]
+    def VerifyBlockState(self, cache, items, cmts, lists, list_of, s, commit):
+        """VerifyBlockFullCached (cache None: VerifyBlockFull) with a deposit's pk address as its second key -> (accepted, [bool], size after or None)"""
+        recs = items if isinstance(items, np.ndarray) else records_from_items(items); recs, ptr, n = _recs(recs)
+        l, keep = _cmt_lists(cmts, lists) if lists is not None else (None, None); lo = np.ascontiguousarray(list_of, dtype=np.int32) if list_of is not None else None; assert lo is None or lo.shape == (n,)
+        ok = (ctypes.c_ubyte * max(1, n))(); size = ctypes.c_longlong(-7); self.L.verifyBlockState.restype = ctypes.c_int
+        rc = self.L.verifyBlockState(_cache_handle(cache), ptr, n, ctypes.byref(l) if l is not None else None, lo.ctypes.data_as(ctypes.c_void_p) if lo is not None and n else None, ctypes.c_void_p(s) if s else None,
+                                     int(bool(commit)), ok, ctypes.byref(size))
         return rc, [bool(ok[i]) for i in range(n)], (None if size.value == -7 else int(size.value))
     # include/zk_proof_cache.h: the proofs the pool has verified are not verified again with their block.  cache: a ProofCache, a handle of ProofCacheNew, or None
     def ProofCacheNew(self, capacity):

@@ -13,7 +13,7 @@
  *
  * Deposit's one-time pk address lives in the same account space in the reference.  It is NOT part of a record's check here: with two keys a record, whether one record
  * is accepted would depend on whether an earlier one was, one after the other through the block.  A caller that wants pk checked passes those addresses (20 bytes at
- * offset 12 of a 32-byte entry) through zkSnSetSpend in a call of its own.
+ * offset 12 of a 32-byte entry) through zkSnSetSpend in a call of its own.  zk_spent_pk.h has the calls that decide both keys of a record together, as the reference does.
  *
  * A call is an upload, three kernel launches and a download whatever the number of keys, and whatever the size of the set: measured on one MI355X 0.03 ms for one
  * key, 0.06 ms for 8,192 and 0.13-0.18 ms for 65,536 (profiles/snset.txt; DESIGN.md "Spent serial numbers").  Against a hash map on one host core that is 6-8 times

@@ -262,6 +262,20 @@ int zkgpu_test_snset_slots(zkgpu_snset *s, uint32_t *slots, uint64_t *n_slots, u
 int zkgpu_test_snset_launches(uint64_t *launches);
 int zkgpu_test_snset_host(const uint8_t *resident, size_t n_resident, const uint8_t exempt[20], const uint8_t *keys, const uint8_t *mask, size_t n, int commit,
                           uint8_t *conflict, uint8_t *appended, size_t *n_appended);
+/* The same loop with up to two keys a record (DESIGN.md "Two keys a record"; the drop-in level is zk_spent_pk.h).  keys: n x 2 x 20 bytes, k1 then k2; nkeys[i] = 0
+ * (masked out), 1 or 2.  The exempt key applies to k1 only: an exempt k1 is neither checked nor inserted, the record's k2 still is.  In record order: conflict[i] = 1
+ * if a key of the record was in the set before the call, or its k2 is the exempt key; else 2 if an earlier ACCEPTED record of this call inserted one of its keys, or
+ * k1 == k2; else 0: the record is accepted and, with commit, its keys are appended, k1 before k2.  A rejected record inserts nothing.  With every nkeys[i] <= 1 the
+ * codes, the log and the size are those of zkgpu_snset_spend.  ZKGPU_ERR_ARG also for nkeys[i] > 2 and unless size + 2n < 2^32 - 2; the call needs live entries +
+ * tombstones + 2n at or below half of the slots.  Four launches a round whatever n is, one round when the batch has no conflict among its own keys; after the round
+ * cap (8) the host decides the records still open.  A committing call may leave tombstones where rejected records had claimed slots. */
+int zkgpu_snset_spend_pairs(zkgpu_snset *s, const uint8_t *keys, const uint8_t *nkeys, size_t n, int commit, uint8_t *conflict, uint64_t *size_out);
+/* test entries: the sequential model of the call above (stateless, host only; appended: room for n x 2 x 20); the round cap of one set (0 = the default); the
+ * process-wide numbers of rounds run on the device and of calls the host finished */
+int zkgpu_test_snset_host_pairs(const uint8_t *resident, size_t n_resident, const uint8_t exempt[20], const uint8_t *keys, const uint8_t *nkeys, size_t n, int commit,
+                                uint8_t *conflict, uint8_t *appended, size_t *n_appended);
+int zkgpu_test_snset_round_cap(zkgpu_snset *s, uint32_t rounds);
+int zkgpu_test_snset_rounds(uint64_t *rounds, uint64_t *host_finishes);
 
 /* ---- the proof cache (DESIGN.md "Proof cache"; the drop-in level is zk_proof_cache.h) --------------------------------------------------------------------
  * The records whose proof this process has accepted, by key: the first 20 bytes of SHA-256(salt[32] || vktag[32] || record[720]) — salt from getrandom at creation,
