@@ -12,6 +12,8 @@ namespace zk {
 void probe_field(int field, int op, const uint8_t *a, const uint8_t *b, uint8_t *out, size_t n);
 void probe_fq2(int op, const uint8_t *a, const uint8_t *b, uint8_t *out, size_t n);
 void probe_group(int group, int op, const uint8_t *a, const uint8_t *b, uint8_t *out, size_t n);
+void probe_field29(int field, int op, const uint32_t *a, const uint32_t *b, const uint32_t *c, const uint32_t *d, uint32_t *out, size_t n);
+void probe_point29(int op, const uint32_t *a, const uint32_t *b, uint32_t *out, uint32_t *flags, size_t n);
 }
 using namespace zk;
 using namespace zk::host;
@@ -74,6 +76,12 @@ int zkgpu_test_fq2_op(int op, const uint8_t *a, const uint8_t *b, uint8_t *out, 
 }
 int zkgpu_test_group_op(int group, int op, const uint8_t *a, const uint8_t *b, uint8_t *out, size_t n) {
   return guarded([&] { probe_group(group, op, a, b, out, n); return ZKGPU_OK; });
+}
+int zkgpu_test_field29_op(int field, int op, const uint32_t *a, const uint32_t *b, const uint32_t *c, const uint32_t *d, uint32_t *out, size_t n) {
+  return guarded([&] { probe_field29(field, op, a, b, c, d, out, n); return ZKGPU_OK; });
+}
+int zkgpu_test_point29_op(int op, const uint32_t *a, const uint32_t *b, uint32_t *out, uint32_t *flags, size_t n) {
+  return guarded([&] { probe_point29(op, a, b, out, flags, n); return ZKGPU_OK; });
 }
 
 zkgpu_msm *zkgpu_msm_create(int group, const uint8_t *points, size_t n, int window_bits, int filter_ones) {

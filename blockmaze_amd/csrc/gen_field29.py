@@ -9,7 +9,8 @@ With 29-bit limbs a column of the product — at most 9 + 9 terms below 2^60 —
 Representation: value v (mod p) is kept as ANY integer x = v * 2^261 (mod p), 0 <= x < 2^261, in limbs l[0..8], x = sum l[i] 2^(29 i).  "Normalized" = limbs 0..7 below
 2^29 + 8 (the top limb holds the rest).  Products take normalized operands (one of them may have limbs up to 2^31.4) and return exactly-29-bit limbs and a value below
 (a b) / 2^261 + p.  A difference a - b is computed as a + K_c - b with K_c = c p written with every low limb in [3 * 2^29 + 64, 4 * 2^29) ("borrow adjusted"), so that
-no limb goes negative when b's limbs are below 3 * (2^29 + 8) and b's value is below c p.  The value bounds of the mixed addition's intermediate results are checked
+no limb goes negative when b's limbs 0..7 are below 3 * (2^29 + 8) and b's top limb is at most K_c's — a few units short of c p's, since K_c lends 3 or 4 units of every
+limb to the one below: any value below (c - 0.01) p keeps to it, a value just under c p does not.  The value bounds of the mixed addition's intermediate results are checked
 below by interval arithmetic (BOUNDS); they stay under 11 p < 2^258.
 """
 Q = 21888242871839275222246405745257275088696311157297823662689037894645226208583
@@ -25,7 +26,8 @@ def adjusted(c):
     assert l[NL - 1] > 0 and sum(v << (B * i) for i, v in enumerate(l)) == c * Q
     return l
 def adjusted_light(c):
-    """c*p with limbs 0..7 in [2^29 + 64, 2 * 2^29 + 64): a + KL - t has no negative limb for t with exact 29-bit limbs (a product's result) and value below c p"""
+    """c*p with limbs 0..7 in [2^29 + 64, 2 * 2^29 + 64): a + KL - t has no negative limb for t with exact 29-bit limbs (a product's result) and a top limb at most KL's (any value below
+    (c - 0.01) p; KL's top limb is one or two units short of c p's)"""
     l = limbs29(c * Q); lo = (1 << B) + 64
     for i in range(NL - 1):
         n = 1 if l[i] + (1 << B) >= lo else 2
@@ -175,7 +177,7 @@ def gen_struct():
     arr("P29", P29, "p"); arr("ONE", ONE29, "2^261 mod p: the field's one"); arr("RCONV", RCONV, "2^256 mod p as a plain integer: a Montgomery product with it turns v 2^261 into v 2^256 (the 8 x 32-bit form)")
     for c, v in KS.items(): arr("K%d" % c, v, "%d p, low limbs in [3 * 2^29 + 64, 4 * 2^29)" % c)
     if EMIT_BARRETT: arr("NP", NP, "2^264 - p (top limb: 32 bits)")
-    arr("KL2", adjusted_light(2), "2 p, low limbs in [2^29 + 64, 2 * 2^29 + 64)"); assert adjusted_light(2)[NL - 1] >= int(1.5 * Q) >> (B * (NL - 1))   # a subtrahend below 1.5 p never exceeds KL2's top limb
+    arr("KL2", adjusted_light(2), "2 p, low limbs in [2^29 + 64, 2 * 2^29 + 64)"); assert adjusted_light(2)[NL - 1] >= int(1.99 * Q) >> (B * (NL - 1))   # a subtrahend below 1.99 p never exceeds KL2's top limb (one just under 2 p does)
     def mads(pairs, const_b, first):
         """one asm statement: acc (+)= sum of the pairs' products; no carries: the column stays below 2^64"""
         txt = " ".join('"v_mad_u64_u32 %%0, vcc, %%%d, %%%d, %s\\n\\t"' % (1 + 2 * i, 2 + 2 * i, "0" if first and i == 0 else "%0") for i in range(len(pairs)))
@@ -216,7 +218,7 @@ def gen_struct():
     #pragma unroll
         for (int i = 1; i < 8; i++) r.l[i] = (l[i] & MASK) + (l[i - 1] >> 29);
         r.l[8] = l[8] + (l[7] >> 29); return r; }
-""" + ("""      // a - b (mod p) as a + K_C - b, normalized.  b: limbs below 3 * (2^29 + 8), value below C p
+""" + ("""      // a - b (mod p) as a + K_C - b, normalized.  b: limbs 0..7 below 3 * (2^29 + 8), top limb at most K_C's (any value below (C - 0.01) p)
       template <int C> static __device__ __forceinline__ Fq29 sub(const Fq29 &a, const Fq29 &b) { Fq29 d;
     #pragma unroll
         for (int i = 0; i < 9; i++) d.l[i] = a.l[i] + (C == 2 ? K2[i] : C == 4 ? K4[i] : C == 6 ? K6[i] : C == 12 ? K12[i] : K18[i]) - b.l[i];
@@ -226,12 +228,12 @@ def gen_struct():
     #pragma unroll
         for (int i = 0; i < 9; i++) r.l[i] = neg ? K2[i] - a.l[i] : a.l[i];
         return r; }
-""" if KS else "") + """      // a - t (mod p) as a + KL_2 - t for a product's result t (exact 29-bit limbs, value below 2 p); limbs of the difference: a's + 2^30 + 64 at most, NOT normalized
+""" if KS else "") + """      // a - t (mod p) as a + KL_2 - t for a product's result t (exact 29-bit limbs, top limb at most KL_2's: any value below 1.99 p); limbs of the difference: a's + 2^30 + 64 at most, NOT normalized
       static __device__ __forceinline__ Fq29 sub_product(const Fq29 &a, const Fq29 &t) { Fq29 d;
     #pragma unroll
         for (int i = 0; i < 9; i++) d.l[i] = a.l[i] + KL2[i] - t.l[i];
         return d; }
-      // KL_2 - t: minus a product's result (limbs below 2^30 + 64: fine as ONE operand of a product)
+      // KL_2 - t: minus a product's result with a top limb at most KL_2's (limbs below 2^30 + 64: fine as ONE operand of a product)
       static __device__ __forceinline__ Fq29 neg_product(const Fq29 &t) { Fq29 d;
     #pragma unroll
         for (int i = 0; i < 9; i++) d.l[i] = KL2[i] - t.l[i];

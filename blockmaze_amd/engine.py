@@ -56,6 +56,24 @@ def group_op(group, op, a, b=None):
         bb = np.ascontiguousarray(b, dtype=np.uint64) if b is not None else None
     _check(lib().zkgpu_test_group_op(group, {"add": 0, "dbl": 1, "madd": 2, "mul_small": 3}[op], _bytes(a), _bytes(bb) if bb is not None else None, _bytes(out), ctypes.c_size_t(n))); return out
 
+# raw-limb probes of the 29-bit-limb arithmetic (csrc/probe29.hip): uint32 arrays, nine limbs an element, nothing converted on the way
+FIELD29_OPS = {"mul": 0, "mul2": 1, "sqr": 2, "norm": 3, "sub2": 4, "sub4": 5, "sub6": 6, "sub12": 7, "sub18": 8, "cond_neg": 9, "sub_product": 10, "neg_product": 11,
+               "add_raw": 12, "barrett": 13, "one": 14, "unpack": 15, "pack_words": 16, "to_words": 17, "product_is_zero": 18, "ntt_lazy": 19}
+POINT29_OPS = {"madd": (0, 36, 19, 36), "madd_pp": (1, 36, 19, 36), "dbl_affine": (2, 0, 19, 36), "add": (3, 36, 36, 36), "quad_add": (4, 36, 36, 36), "quad_add_opp": (5, 36, 36, 36),
+               "oct_add": (6, 72, 72, 72), "fq2_mul": (7, 18, 18, 18), "fq2_sqr": (8, 18, 0, 18), "g2_madd": (9, 72, 37, 72), "madd_chain": (10, 36, 19 * 32, 36 * 32)}   # code, words a point: a, b, out
+def _u32(a): return a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)) if a is not None else None
+def field29_op(field, op, a, b=None, c=None, d=None):
+    """field 0 = Fr29, 1 = Fq29; operands (n, 9) uint32.  Returns (n, 9) uint32 ((n, 45) for ntt_lazy)."""
+    ops = [np.ascontiguousarray(x, dtype=np.uint32) if x is not None else None for x in (a, b, c, d)]; n = ops[0].shape[0]
+    assert all(x is None or x.shape == (n, 9) for x in ops); out = np.zeros((n, 45 if op == "ntt_lazy" else 9), dtype=np.uint32)
+    _check(lib().zkgpu_test_field29_op(int(field), FIELD29_OPS[op], _u32(ops[0]), _u32(ops[1]), _u32(ops[2]), _u32(ops[3]), _u32(out), ctypes.c_size_t(n))); return out
+def point29_op(op, a, b=None):
+    """a, b: (n, words) uint32 as POINT29_OPS says (the one an operation does not take: None).  Returns (limbs (n, words out), flags (n,))"""
+    code, wa, wb, wo = POINT29_OPS[op]; a = np.ascontiguousarray(a, dtype=np.uint32) if wa else None; b = np.ascontiguousarray(b, dtype=np.uint32) if wb else None
+    n = (a if wa else b).shape[0]; assert (not wa or a.shape == (n, wa)) and (not wb or b.shape == (n, wb))
+    out = np.zeros((n, wo), dtype=np.uint32); flags = np.zeros(n, dtype=np.uint32)
+    _check(lib().zkgpu_test_point29_op(code, _u32(a), _u32(b), _u32(out), _u32(flags), ctypes.c_size_t(n))); return out, flags
+
 def msm(group, points, scalars, window_bits=0, filter_ones=False):
     points = np.ascontiguousarray(points, dtype=np.uint64); scalars = np.ascontiguousarray(scalars, dtype=np.uint64); n = scalars.size // 4
     out = np.zeros(8 if group == 1 else 16, dtype=np.uint64)

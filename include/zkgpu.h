@@ -47,6 +47,20 @@ int zkgpu_test_field_op(int field, int op, const uint8_t *a, const uint8_t *b, u
 int zkgpu_test_fq2_op(int op, const uint8_t *a, const uint8_t *b, uint8_t *out, size_t n);
 /* group: 1 = G1, 2 = G2.  op: 0 general add, 1 double(a), 2 mixed add (b affine), 3 a*k for 32-bit k (k in b's first 4 bytes) */
 int zkgpu_test_group_op(int group, int op, const uint8_t *a, const uint8_t *b, uint8_t *out, size_t n);
+/* Raw-limb probes of the arithmetic on nine 29-bit limbs (field29_gfx950.inc) and of the point formulas built on it: nothing is converted or normalized on the
+   way, an element is its nine uint32 limbs.  field: 0 = Fr29, 1 = Fq29.  a, b, c, d: nine words an element (operands an operation does not take may be null).
+   op: 0 mul(a, b), 1 mul2(a, b, c, d), 2 sqr, 3 norm, 4..8 sub<2 / 4 / 6 / 12 / 18>(a, b), 9 cond_neg(a, bit 0 of b's first word), 10 sub_product(a, b),
+   11 neg_product, 12 add_raw, 13 barrett, 14 one, 15 unpack (eight words in), 16 pack_words, 17 to_words (eight words and a zero out), 18 fq29_product_is_zero
+   (first word out), 19 two lazy butterfly stages of ntt29_lds_pass (Fr29; 45 words out: (a - b) - c | (a + b) + c | either times d | norm(a - the first product)).
+   Fr29 has ops 0, 2, 3, 10, 11, 12, 15, 16, 17 and 19; Fq29 all but 19.  out: nine words an element (op 19: 45). */
+int zkgpu_test_field29_op(int field, int op, const uint32_t *a, const uint32_t *b, const uint32_t *c, const uint32_t *d, uint32_t *out, size_t n);
+/* op: 0 XYZZ29 madd_head + madd_tail, 1 madd_head + madd_tail_pp (flags: bit 0 P^2 = 0, bit 1 R^2 = 0 mod q), 2 xyzz29_dbl_affine(b), 3 xyzz29_add (flags bit 1: ZZ = 0
+   mod q), 4 quad29_add<false>, 5 quad29_add<true>, 6 oct29_add (4 .. 6: flags bit 0 = the sum is the point at infinity; an operand with all-zero ZZ limbs is the
+   point at infinity), 7 fq2_29_mul, 8 fq2_29_sqr, 9 XYZZ2_29::madd, 10 a run of 32 mixed additions into one accumulator, the limbs after every one of them.
+   Words a point (a | b | out): ops 0, 1: 36 | 19 | 36; 2: - | 19 | 36; 3 .. 5: 36 | 36 | 36; 6: 72 | 72 | 72; 7: 18 | 18 | 18; 8: 18 | - | 18; 9: 72 | 37 | 72; 10: 36 | 32 x 19 | 32 x 36.
+   G1: X Y ZZ ZZZ; affine operand: x y sign (bit 0: add the negative).  G2 in op 9: X.c0 X.c1 Y.c0 .. ZZZ.c1, affine x.c0 x.c1 y.c0 y.c1 sign; in op 6 component-major,
+   X.c0 Y.c0 ZZ.c0 ZZZ.c0 X.c1 .. ZZZ.c1 (the slots of the eight lanes).  flags: one word a point. */
+int zkgpu_test_point29_op(int op, const uint32_t *a, const uint32_t *b, uint32_t *out, uint32_t *flags, size_t n);
 
 /* ---- multi-scalar multiplication ------------------------------------------------------------------------------------ */
 /* window_bits 0 = choose from n.  filter_ones: bit 0 = treat scalars 0 / 1 specially like multi_exp_with_mixed_addition; bit 1 = the scalars are known to be

@@ -175,6 +175,17 @@ def test_domain_transforms_match_oracle(m):
     for op in ("fft", "ifft", "cosetfft", "icosetfft"):
         assert np.array_equal(e.domain_transform(m, op, a), o.domain_op(op, m, a)), (m, op)
 
+@pytest.mark.parametrize("m", [16, 64, 1024, 4096, 5120, 1 << 13])
+def test_domain_transforms_match_oracle_at_the_top_of_the_field(m):
+    """coefficients that push the lazy butterflies of the tiles (ntt.cuh: no reduction inside a tile, "25 r after eleven stages") towards their bound, where random
+    ones stay in the middle: every element r - 1, 0 and r - 1 in turn, and a single r - 1 at index 0, 1 and m - 1"""
+    n = o.domain_size(m); top = o.R_MOD - 1; pats = {"all": [top] * n, "alternating": [top * (i & 1) for i in range(n)]}
+    for k in (0, 1, n - 1): pats["impulse at %d" % k] = [top * (i == k) for i in range(n)]
+    for name, vals in pats.items():
+        a = o.to_arr(vals)
+        for op in ("fft", "ifft", "cosetfft", "icosetfft"):
+            assert np.array_equal(e.domain_transform(m, op, a), o.domain_op(op, m, a)), (m, name, op)
+
 @pytest.mark.parametrize("m", [1 << 18, (1 << 17) + (1 << 16)])
 def test_domain_roundtrip_at_scale(m):
     """send-sized (2^18) and mint-sized (196,608, step) domains: iFFT(FFT(a)) == a, icosetFFT(cosetFFT(a)) == a"""
