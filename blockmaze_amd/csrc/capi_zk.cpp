@@ -37,6 +37,7 @@
 #include "../../include/zk_spent.h"
 #include "../../include/zk_proof_cache.h"
 #include "../../include/zk_spent_pk.h"
+#include "../../include/zk_tree_block.h"
 #include "../../include/zkgpu.h"
 #include "blockmaze_circuits.hpp"
 #include "groth16.hpp"
@@ -1270,12 +1271,13 @@ static void records_for_per_proof(const zk_block_record *recs, const int *idx, s
 // alpha_beta^s into one right-hand side, and the block takes ONE final exponentiation.  Every other kind — a small one, one whose key fails rlc_key_ok, one with no
 // record in the equation or a sum at infinity — goes through verify_group exactly as in verifyBatch, and so does every kind of the equation if the equation fails or
 // a device step throws.
-static int verify_block_records(const zk_block_record *recs, int n, unsigned char *ok, const char *who) {
+// (depth: the Merkle depth whose key the deposit records are verified with; 8 = depositvk.txt, every entry but verifyBlockTree)
+static int verify_block_records(const zk_block_record *recs, int n, unsigned char *ok, const char *who, size_t depth = 8) {
   try {
     struct Group { CircuitKind kind; std::string path; std::vector<int> idx; std::vector<uint8_t> res; size_t ni = 0; RlcPart part; bool in_eq = false, decided = false; };
     std::vector<Group> groups; std::vector<int> idx[4];
     for (int i = 0; i < n; i++) { ok[i] = 0; if (recs[i].kind <= 3) idx[recs[i].kind].push_back(i); }
-    for (int k = 0; k < 4; k++) { if (idx[k].empty()) continue; Group g; g.kind = (CircuitKind)k; g.path = key_path(g.kind, false); g.idx = std::move(idx[k]);
+    for (int k = 0; k < 4; k++) { if (idx[k].empty()) continue; Group g; g.kind = (CircuitKind)k; g.path = key_path(g.kind, false, depth); g.idx = std::move(idx[k]);
       g.ni = record_num_inputs(k); g.res.assign(g.idx.size(), 0); groups.push_back(std::move(g)); }
     const bool one_kind = groups.size() == 1 && groups[0].idx.size() == (size_t)n;       // (a block of one kind is staged with one copy)
     bool any_eq = false;
@@ -1304,7 +1306,7 @@ static int verify_block_records(const zk_block_record *recs, int n, unsigned cha
     for (Group &g : groups) if (!g.decided) {
       std::vector<Proof> ps; std::vector<uint8_t> parsed; std::vector<Fe32> inputs;
       records_for_per_proof(recs, one_kind ? nullptr : g.idx.data(), g.idx.size(), g.kind, ps, parsed, inputs, true);
-      verify_group(g.kind, ps.data(), parsed.data(), inputs.data(), g.ni, g.idx.size(), g.res.data());
+      verify_group(g.kind, ps.data(), parsed.data(), inputs.data(), g.ni, g.idx.size(), g.res.data(), depth);
     }
     int accepted = 0;
     for (Group &g : groups) for (size_t j = 0; j < g.idx.size(); j++) { ok[g.idx[j]] = g.res[j]; accepted += g.res[j]; }
@@ -1342,14 +1344,14 @@ static void record_digests(const uint8_t salt[32], const uint8_t (*tags)[32], ui
 // without its mutex, so two threads may both verify a record — it is then stored once.  The cache never costs a decision: if a step of it throws, every record is
 // treated as a miss and nothing is stored, which is the uncached entry.  A kind's tag is read before verification and again after it, and its records are stored only
 // if the two are equal: a key file replaced during the call stores nothing under either name.
-static int verify_block_records_cached(zkgpu_proof_cache *cache, const zk_block_record *recs, int n, unsigned char *ok, const char *who) {
-  if (!cache || n <= 0 || !gpu_available()) return verify_block_records(recs, n, ok, who);
+static int verify_block_records_cached(zkgpu_proof_cache *cache, const zk_block_record *recs, int n, unsigned char *ok, const char *who, size_t depth = 8) {
+  if (!cache || n <= 0 || !gpu_available()) return verify_block_records(recs, n, ok, who, depth);
   const size_t N = (size_t)n; std::vector<uint8_t> keys, has_key, hit; uint8_t tags[4][32]; uint32_t kinds = 0; bool usable = false; size_t n_hit = 0;
   try {
     has_key.assign(N, 0); hit.assign(N, 0); bool present[4] = {false, false, false, false};
     for (size_t i = 0; i < N; i++) if (recs[i].kind <= 3) present[recs[i].kind] = true;
     for (int k = 0; k < 4; k++) if (present[k]) {                                         // (a kind whose key cannot be loaded has no key: its records go to verification as they are)
-      try { vk_for_path(key_path((CircuitKind)k, false), tags[k]); kinds |= 1u << k; } catch (const std::exception &) {} }
+      try { vk_for_path(key_path((CircuitKind)k, false, depth), tags[k]); kinds |= 1u << k; } catch (const std::exception &) {} }
     if (kinds) {
       HostSpan span("host.cache_lookup");
       keys.resize(20 * N); record_digests(cache->c.salt(), tags, kinds, recs, N, N >= DIGEST_DEVICE_MIN, keys.data());
@@ -1363,25 +1365,25 @@ static int verify_block_records_cached(zkgpu_proof_cache *cache, const zk_block_
   catch (const std::exception &e) { fprintf(stderr, "libzkgpu: %s: the proof cache failed (%s); verifying every record\n", who, e.what()); usable = false; n_hit = 0; }
   catch (...) { fprintf(stderr, "libzkgpu: %s: the proof cache failed; verifying every record\n", who); usable = false; n_hit = 0; }
   int rc;
-  if (!n_hit) rc = verify_block_records(recs, n, ok, who);
+  if (!n_hit) rc = verify_block_records(recs, n, ok, who, depth);
   else {
     try {
       std::vector<zk_block_record> miss; std::vector<size_t> idx; miss.reserve(N - n_hit); idx.reserve(N - n_hit);
       { HostSpan span("host.cache_gather"); for (size_t i = 0; i < N; i++) if (!hit[i]) { miss.push_back(recs[i]); idx.push_back(i); } }
       std::vector<unsigned char> mok(miss.size() + 1, 0);
-      rc = miss.empty() ? 0 : verify_block_records(miss.data(), (int)miss.size(), mok.data(), who);   // (a block of hits alone runs no verifier at all)
+      rc = miss.empty() ? 0 : verify_block_records(miss.data(), (int)miss.size(), mok.data(), who, depth);   // (a block of hits alone runs no verifier at all)
       if (rc < 0) { for (int i = 0; i < n; i++) ok[i] = 0; return -1; }
       for (size_t i = 0; i < N; i++) ok[i] = hit[i] ? 1 : 0;
       for (size_t j = 0; j < idx.size(); j++) ok[idx[j]] = mok[j];
       rc += (int)n_hit;
     }
-    catch (const std::exception &e) { fprintf(stderr, "libzkgpu: %s: the proof cache failed (%s); verifying every record\n", who, e.what()); return verify_block_records(recs, n, ok, who); }
+    catch (const std::exception &e) { fprintf(stderr, "libzkgpu: %s: the proof cache failed (%s); verifying every record\n", who, e.what()); return verify_block_records(recs, n, ok, who, depth); }
   }
   if (rc < 0 || !usable) return rc;
   try {
     bool same[4] = {false, false, false, false};
     for (int k = 0; k < 4; k++) if ((kinds >> k) & 1u) { uint8_t t[32];
-      try { vk_for_path(key_path((CircuitKind)k, false), t); same[k] = !memcmp(t, tags[k], 32); } catch (const std::exception &) {} }
+      try { vk_for_path(key_path((CircuitKind)k, false, depth), t); same[k] = !memcmp(t, tags[k], 32); } catch (const std::exception &) {} }
     std::vector<uint8_t> mask(N, 0); bool any = false;
     for (size_t i = 0; i < N; i++) { mask[i] = has_key[i] && !hit[i] && ok[i] && same[recs[i].kind]; any |= mask[i] != 0; }
     if (any) { HostSpan span("host.cache_insert"); cache->c.insert(keys.data(), mask.data(), N); }
@@ -1512,6 +1514,12 @@ int zkgpu_tree_find_at(zkgpu_tree *t, uint64_t size, const uint8_t leaf[32], uin
   *index = got; return ZKGPU_OK; }); }
 int zkgpu_tree_rewind(zkgpu_tree *t, uint64_t size) { return guarded_tree(t, [&] {
   if (!t->t.rewind(size)) { zkgpu_set_error("commitment tree: cannot rewind to " + std::to_string(size) + " leaves, the tree holds fewer"); return ZKGPU_ERR_ARG; }
+  return ZKGPU_OK; }); }
+// anchors (DESIGN.md "A block against the resident tree"): sizes are checked under the tree's lock, before anything is queued
+int zkgpu_tree_match_roots(zkgpu_tree *t, const uint64_t *sizes, size_t n_sizes, const uint8_t *rts, size_t n, int hash_order, int32_t *match_out) { return guarded_tree(t, [&] {
+  if ((n_sizes && !sizes) || (n && (!rts || !match_out))) { zkgpu_set_error("commitment tree: a null pointer"); return ZKGPU_ERR_ARG; }
+  if (n_sizes >= (1ull << 31)) { zkgpu_set_error("commitment tree: 2^31 anchors or more"); return ZKGPU_ERR_ARG; }
+  if (!t->t.match_roots(sizes, n_sizes, rts, n, hash_order != 0, match_out)) { zkgpu_set_error("commitment tree: a size above the tree's size"); return ZKGPU_ERR_ARG; }
   return ZKGPU_OK; }); }
 int zkgpu_test_tree_state_launches(zkgpu_tree *t, uint64_t *launches) { return guarded_tree(t, [&] { if (!launches) return ZKGPU_ERR_ARG; *launches = t->t.state_launches(); return ZKGPU_OK; }); }
 int zkgpu_test_tree_host(int depth, const uint8_t *leaves, size_t n, uint64_t index, uint8_t root[32], uint8_t *path) { return guarded_host([&] {
@@ -1823,11 +1831,10 @@ long long zkSnSetSpendPairs(zk_snset *set, const uint8_t *sns, const uint8_t *pk
   if (rc != ZKGPU_OK) { fprintf(stderr, "libzkgpu: zkSnSetSpendPairs: %s\n", zkgpu_last_error()); return -1; }
   return (long long)size;
 }
-// block_full with the spend step on pairs: a deposit brings its one-time pk address (args[1][0..19]) as second key
-int verifyBlockState(zk_proof_cache *cache, const zk_block_record *recs, int n, const zk_cmt_lists *l, const int32_t *list_of, zk_snset *set, int commit, unsigned char *ok,
-                     long long *size_out) {
-  const int accepted = block_records_roots(recs, n, l, list_of, ok, cache); if (accepted < 0 || !set) return accepted;
-  uint64_t size = 0; std::vector<uint8_t> conflict;
+// the spend step on pairs: a record with ok[i] = 0 brings no key, a deposit its serial number and its one-time pk address (args[1][0..19]), every other record its
+// serial number.  A record in conflict loses its ok.  Returns the records still accepted, or -1 with every ok[i] = 0 and the set unchanged.
+static int block_spend_pairs(const zk_block_record *recs, int n, zk_snset *set, int commit, unsigned char *ok, uint64_t &size, const char *who) {
+  std::vector<uint8_t> conflict;
   const int rc = guarded_snset(set, [&] {
     std::vector<uint8_t> keys((size_t)40 * n), nkeys((size_t)n); conflict.resize((size_t)n);
     { HostSpan span("host.sn_keys");
@@ -1837,10 +1844,84 @@ int verifyBlockState(zk_proof_cache *cache, const zk_block_record *recs, int n, 
       } }
     if (!set->s.spend_pairs(keys.data(), nkeys.data(), (size_t)n, commit != 0, conflict.data(), &size)) { zkgpu_set_error("the log could reach 2^32 - 2 entries"); return ZKGPU_ERR_ARG; }
     return ZKGPU_OK; });
-  if (rc != ZKGPU_OK) { fprintf(stderr, "libzkgpu: verifyBlockState: %s\n", zkgpu_last_error()); for (int i = 0; i < n; i++) ok[i] = 0; return -1; }
+  if (rc != ZKGPU_OK) { fprintf(stderr, "libzkgpu: %s: %s\n", who, zkgpu_last_error()); for (int i = 0; i < n; i++) ok[i] = 0; return -1; }
   int still = 0; for (int i = 0; i < n; i++) { if (conflict[i]) ok[i] = 0; still += ok[i] != 0; }
+  return still;
+}
+// block_full with the spend step on pairs
+int verifyBlockState(zk_proof_cache *cache, const zk_block_record *recs, int n, const zk_cmt_lists *l, const int32_t *list_of, zk_snset *set, int commit, unsigned char *ok,
+                     long long *size_out) {
+  const int accepted = block_records_roots(recs, n, l, list_of, ok, cache); if (accepted < 0 || !set) return accepted;
+  uint64_t size = 0; const int still = block_spend_pairs(recs, n, set, commit, ok, size, "verifyBlockState"); if (still < 0) return -1;
   if (size_out) *size_out = (long long)size;
   return still;
+}
+
+// ---- a block against the resident tree (DESIGN.md "A block against the resident tree"; include/zk_tree_block.h) -----------------------------------------------
+// verifyBlockState's steps with the deposit key of the tree's depth, the anchor step on the device in place of the depth-8 lists, and the accepted sends' cmtS
+// appended at the end.  The tree's mutex is held only inside size(), match_roots() and append(), never together with the cache's or the set's.
+int verifyBlockTree(zk_proof_cache *cache, const zk_block_record *recs, int n, zk_tree *tree, const long long *anchors, int n_anchors, zk_snset *set, int commit,
+                    unsigned char *ok, int32_t *anchor_of, long long *set_size_out, long long *tree_size_out) {
+  if (!tree) {
+    if (anchor_of) for (int i = 0; i < n; i++) anchor_of[i] = -1;
+    if (tree_size_out) *tree_size_out = -1;
+    return verifyBlockState(cache, recs, n, nullptr, nullptr, set, commit, ok, set_size_out);
+  }
+  auto fail = [&](const std::string &why) {
+    zkgpu_set_error(why); fprintf(stderr, "libzkgpu: verifyBlockTree: %s\n", why.c_str());
+    for (int i = 0; i < n; i++) { if (ok) ok[i] = 0; if (anchor_of) anchor_of[i] = -1; }
+    return -1; };
+  try {
+    // 1. the arguments, before anything is queued
+    if (n < 0 || (n && (!recs || !ok))) return fail("a negative count or a null pointer");
+    if (n_anchors < 0 || (n_anchors && !anchors)) return fail("a negative number of anchors or a null pointer");
+    if (!gpu_available()) return fail("no HIP device visible; libzkgpu has no CPU fallback");
+    const size_t depth = (size_t)tree->t.depth(); const uint64_t size0 = tree->t.size();
+    std::vector<uint64_t> sizes((size_t)n_anchors);
+    for (int a = 0; a < n_anchors; a++) {
+      if (anchors[a] < 0 || (uint64_t)anchors[a] > size0) return fail("anchor " + std::to_string(a) + " is negative or above the tree's size");
+      sizes[a] = (uint64_t)anchors[a]; }
+    if (commit) {
+      uint64_t sends = 0; for (int i = 0; i < n; i++) sends += recs[i].kind == ZK_KIND_SEND;
+      if (sends > (1ull << depth) - size0) return fail("the block's sends do not fit into the tree");
+    }
+    for (int i = 0; i < n; i++) if (anchor_of) anchor_of[i] = -1;
+    // 2. the proof step, the deposits under the key of the tree's depth
+    if (verify_block_records_cached(cache, recs, n, ok, "verifyBlockTree", depth) < 0) return fail(zkgpu_last_error());
+    // 3. the anchor step: the RTs of the deposits still accepted, against the roots at the anchors
+    std::vector<int> at; std::vector<uint8_t> gathered;
+    { HostSpan span("host.tree_gather");
+      for (int i = 0; i < n; i++) if (ok[i] && recs[i].kind == ZK_KIND_DEPOSIT) { at.push_back(i); gathered.insert(gathered.end(), recs[i].args[0], recs[i].args[0] + 32); } }
+    if (!at.empty()) {
+      std::vector<int32_t> match(at.size(), -1);
+      if (!tree->t.match_roots(sizes.data(), sizes.size(), gathered.data(), at.size(), true, match.data())) return fail("an anchor is above the tree's size: the tree was rewound during the call");
+      for (size_t j = 0; j < at.size(); j++) { if (match[j] < 0) ok[at[j]] = 0; else if (anchor_of) anchor_of[at[j]] = match[j]; }
+    }
+    // 4. the spend step
+    int accepted = 0; uint64_t set_size = 0, set_before = 0;
+    if (set) {
+      if (commit) set_before = set->s.size();
+      accepted = block_spend_pairs(recs, n, set, commit, ok, set_size, "verifyBlockTree"); if (accepted < 0) return fail(zkgpu_last_error());   // (a deposit that loses here keeps the anchor it matched)
+    } else for (int i = 0; i < n; i++) accepted += ok[i] != 0;
+    // 5. the append step: the cmtS of the sends still accepted, as zkTreeAppend makes its leaves, in one append
+    if (commit) {
+      gathered.clear();
+      { HostSpan span("host.tree_gather");
+        for (int i = 0; i < n; i++) if (ok[i] && recs[i].kind == ZK_KIND_SEND) for (int b = 0; b < 32; b++) gathered.push_back(recs[i].args[2][31 - b]); }
+      bool appended = false; std::string why = "the tree is full: another writer appended during the call";
+      try { appended = tree->t.append(gathered.empty() ? nullptr : gathered.data(), gathered.size() / 32); } catch (const std::exception &e) { why = e.what(); }
+      if (!appended) {
+        if (set) { try { set->s.rewind(set_before); } catch (const std::exception &e) { fprintf(stderr, "libzkgpu: verifyBlockTree: the spent set could not be rewound (%s)\n", e.what()); } }
+        return fail(why);
+      }
+    }
+    // 6. the sizes after the call
+    if (set && set_size_out) *set_size_out = (long long)set_size;
+    if (tree_size_out) *tree_size_out = (long long)tree->t.size();
+    return accepted;
+  }
+  catch (const std::exception &e) { return fail(e.what()); }
+  catch (...) { return fail("unknown error"); }
 }
 
 // ---- the proof cache (DESIGN.md "Proof cache"; include/zkgpu.h, include/zk_proof_cache.h) ----------------------------------------------------------------------

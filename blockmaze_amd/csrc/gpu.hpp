@@ -189,6 +189,10 @@ class CommitmentTree {
   // before anything is queued — false: a size above size(), an index not below its size, a null pointer; nothing is written and nothing changes then — and is at
   // most two kernel launches and one download whatever q is.
   bool roots_at(const uint64_t *sizes, size_t q, uint8_t *out /* q x 32 */);                       // one launch; sizes may repeat and come in any order
+  // match_out[i] = the lowest a with root(sizes[a]) == RT i, or -1 (DESIGN.md "A block against the resident tree").  rts: q x 32 bytes in blob order, or
+  // (hash_order) as the bytes of the common.Hash.  One upload, two launches — roots_at's kernel, then the compare, which reads the roots from device memory — and
+  // q x 4 bytes back; q = 0 or m = 0 launches nothing (m = 0: all -1).  false also for m >= 2^31.
+  bool match_roots(const uint64_t *sizes, size_t m, const uint8_t *rts, size_t q, bool hash_order, int32_t *match_out);
   bool paths_at(uint64_t size, const uint64_t *indices, size_t q, uint8_t *siblings /* q x depth x 32 */, uint8_t *root /* 32, or null */);
   bool find_at(uint64_t size, const uint8_t leaf[32], uint64_t &index);                           // the first of the first `size` leaves equal to the blob
   bool snapshot_at(uint64_t size, const uint8_t leaf[32], Snapshot &out);                          // snapshot() of state `size`; false also if the tree is smaller

@@ -154,6 +154,56 @@ __global__ void __launch_bounds__(64) k_tree_rewind(TreeGeom G, uint64_t m) {
   tree_edge_walk(G, m, [&](uint32_t k, const Node &B) { tree_store(G.nodes + 32 * (tree_off(G.cap_log, k) + ((m - 1) >> k)), B); });
 }
 
+// ---- anchors (DESIGN.md "A block against the resident tree") --------------------------------------------------------------------------------------------------
+// match[t] = the lowest a < m with roots[a] == RT t, or -1.  roots are the m x 32 bytes that k_tree_roots_at wrote in an EARLIER launch (plain stores are not
+// visible across XCDs inside one launch), in blob order; an RT comes in blob order or (hash_order) as the bytes of its common.Hash: blob word i is then word 7 - i
+// with its bytes swapped, made once, in registers.  One lane a record; the roots pass through LDS in tiles of MATCH_TILE, a barrier before a tile is read and one
+// before it is overwritten.  Inside a tile every lane walks the anchors in index order, eight a step: word 0 first — all lanes read one LDS address, a broadcast — and the other
+// seven only where word 0 is equal; the lowest match stays.  A lane at or beyond q takes part in the tile loads and reaches every barrier; it compares and stores nothing.  No atomics.
+constexpr int MATCH_THREADS = 256, MATCH_TILE = 256;
+__global__ void __launch_bounds__(MATCH_THREADS) k_tree_match_roots(const uint32_t *__restrict__ roots, uint32_t m, const uint32_t *__restrict__ rts, uint64_t q, int hash_order,
+                                                                    int32_t *__restrict__ match) {
+  __shared__ uint32_t tile[8 * MATCH_TILE];
+  const uint32_t tid = threadIdx.x; const uint64_t t = (uint64_t)blockIdx.x * MATCH_THREADS + tid; const bool live = t < q;
+  uint32_t r[8];
+#pragma unroll
+  for (int i = 0; i < 8; i++) r[i] = 0;
+  if (live) {
+    uint32_t w[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) w[i] = rts[8 * t + i];
+#pragma unroll
+    for (int i = 0; i < 8; i++) r[i] = hash_order ? __builtin_bswap32(w[7 - i]) : w[i];
+  }
+  int32_t best = -1;
+#pragma unroll 1
+  for (uint32_t base = 0; base < m; base += MATCH_TILE) {
+    const uint32_t cnt = m - base < (uint32_t)MATCH_TILE ? m - base : (uint32_t)MATCH_TILE;    // (uniform: the barriers below are reached by every lane)
+    __syncthreads();                                                                            // the tile before this one has been read by everyone
+    for (uint32_t i = tid; i < 8 * cnt; i += MATCH_THREADS) tile[i] = roots[8 * (uint64_t)base + i];
+    __syncthreads();
+    if (live && best < 0) {
+      // eight anchors a step: their words 0 are eight independent LDS reads in flight, where one read a step waits out the LDS latency 256 times a tile.  a + j stays
+      // inside the tile whatever cnt is (a is a multiple of 8 below 256); an entry at or beyond cnt is stale and is not looked at.
+#pragma unroll 1
+      for (uint32_t a = 0; a < cnt && best < 0; a += 8) {
+        uint32_t w0[8];
+#pragma unroll
+        for (int j = 0; j < 8; j++) w0[j] = tile[8 * (a + j)];
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+          if (best >= 0 || a + j >= cnt || w0[j] != r[0]) continue;
+          bool same = true;
+#pragma unroll
+          for (int i = 1; i < 8; i++) same &= tile[8 * (a + j) + i] == r[i];
+          if (same) best = (int32_t)(base + a + j);
+        }
+      }
+    }
+  }
+  if (live) match[t] = best;
+}
+
 struct CommitmentTree::Impl {
   std::mutex mu; uint32_t depth = 0, cap_log = 0; uint64_t n = 0; DevBuf<uint8_t> nodes, empty, out, first /* k_tree_find's word */; std::vector<uint8_t> empty_host;
   uint64_t launches = 0, state_launches = 0; DevBuf<uint8_t> q_in, q_out;   // past states: the sizes or indices of a call, and its answer (kept and grown)
@@ -270,6 +320,25 @@ bool CommitmentTree::roots_at(const uint64_t *sizes, size_t q, uint8_t *out) {
   hipLaunchKernelGGL(k_tree_roots_at, dim3((unsigned)cdiv(q, 64)), dim3(64), 0, s, d.geom(), (const unsigned long long *)d.q_in.get(), (uint64_t)q, d.q_out.get()); d.state_launches++;
   HIP_CHECK(hipGetLastError()); d.q_out.download(h.data(), h.size());
   memcpy(out, h.data(), h.size()); return true;
+}
+// The anchor step of a block: one upload [sizes | RTs], k_tree_roots_at as it is — its roots stay in device memory —, then k_tree_match_roots in a launch of its
+// own, which is what makes the roots visible to it, and q x 4 bytes back.
+bool CommitmentTree::match_roots(const uint64_t *sizes, size_t m, const uint8_t *rts, size_t q, bool hash_order, int32_t *match_out) {
+  Impl &d = *impl; std::lock_guard<std::mutex> lk(d.mu);
+  if ((m && !sizes) || (q && (!rts || !match_out)) || m >= (1ull << 31)) return false;
+  for (size_t i = 0; i < m; i++) if (sizes[i] > d.n) return false;
+  if (!q) return true;
+  if (!m) { for (size_t i = 0; i < q; i++) match_out[i] = -1; return true; }
+  LaneScope lane(0); std::lock_guard<std::mutex> gl(g_gpu_mutex); hipStream_t s = gpu().stream;
+  std::vector<uint8_t> up(8 * m + 32 * q); memcpy(up.data(), sizes, 8 * m); memcpy(up.data() + 8 * m, rts, 32 * q);
+  d.grow(d.q_in, up.size()); d.grow(d.q_out, 32 * m + 4 * q); std::vector<int32_t> h(q); Impl::SyncAtExit sync;   // (the vectors outlive the synchronise)
+  HIP_CHECK(hipMemcpyAsync(d.q_in.get(), up.data(), up.size(), hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(k_tree_roots_at, dim3((unsigned)cdiv(m, 64)), dim3(64), 0, s, d.geom(), (const unsigned long long *)d.q_in.get(), (uint64_t)m, d.q_out.get()); d.state_launches++;
+  hipLaunchKernelGGL(k_tree_match_roots, dim3((unsigned)cdiv(q, MATCH_THREADS)), dim3(MATCH_THREADS), 0, s, (const uint32_t *)d.q_out.get(), (uint32_t)m,
+                     (const uint32_t *)(d.q_in.get() + 8 * m), (uint64_t)q, hash_order ? 1 : 0, (int32_t *)(d.q_out.get() + 32 * m)); d.state_launches++;
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipMemcpyAsync(h.data(), d.q_out.get() + 32 * m, 4 * q, hipMemcpyDeviceToHost, s)); HIP_CHECK(hipStreamSynchronize(s));
+  memcpy(match_out, h.data(), 4 * q); return true;
 }
 bool CommitmentTree::paths_at(uint64_t size, const uint64_t *indices, size_t q, uint8_t *siblings, uint8_t *root) {
   Impl &d = *impl; std::lock_guard<std::mutex> lk(d.mu);

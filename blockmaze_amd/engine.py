@@ -348,6 +348,13 @@ class Tree:
     def find_at(self, size, leaf):
         """index of the first of the first `size` leaves equal to the blob; raises ZkGpuError if there is none"""
         i = ctypes.c_uint64(0); _check(lib().zkgpu_tree_find_at(ctypes.c_void_p(self.h), ctypes.c_uint64(size), bytes(leaf), ctypes.byref(i))); return int(i.value)
+    def match_roots(self, sizes, rts, hash_order=False):
+        """for each 32-byte RT the lowest index a with root(sizes[a]) == RT, or -1; two launches.  hash_order: the RTs as the bytes of the common.Hash"""
+        m = np.ascontiguousarray(sizes, dtype=np.uint64).reshape(-1); k = int(m.size); buf = rts if isinstance(rts, (bytes, bytearray)) else b"".join(bytes(x) for x in rts); assert len(buf) % 32 == 0
+        q = len(buf) // 32; out = np.full(max(1, q), -7, dtype=np.int32)
+        _check(lib().zkgpu_tree_match_roots(ctypes.c_void_p(self.h), m.ctypes.data_as(ctypes.c_void_p) if k else None, ctypes.c_size_t(k), bytes(buf) if q else None, ctypes.c_size_t(q), int(bool(hash_order)),
+                                            out.ctypes.data_as(ctypes.c_void_p)))
+        return [int(x) for x in out[:q]]
     def rewind(self, size):
         """the tree goes back to its first `size` leaves"""
         _check(lib().zkgpu_tree_rewind(ctypes.c_void_p(self.h), ctypes.c_uint64(size)))
@@ -649,5 +656,14 @@ class Zk:
         p = self.L.genDepositproofTreeAt(ctypes.c_uint64(value), ctypes.c_uint64(value_old), self.hx(sn_old), self.hx(r_old), self.hx(sn), self.hx(r), self.hx(sns), self.hx(rs), self.hx(cmtB_old), self.hx(cmtB), ctypes.c_uint64(value_s),
                                          self.hx(pk), self.hx(sn_A_old), self.hx(cmtS), self.hx(sk), ctypes.c_void_p(t) if t else None, ctypes.c_longlong(size), rt).decode()
         return p, (bytes.fromhex(rt.value.decode()) if rt.value else None)
+    # include/zk_tree_block.h: a block decided against the resident tree
+    def VerifyBlockTree(self, cache, items, tree, anchors, s, commit):
+        """tree: a handle of TreeNew or None; anchors: tree sizes -> (accepted, [bool], [anchor_of], set size after or None, tree size after or None)"""
+        recs = items if isinstance(items, np.ndarray) else records_from_items(items); recs, ptr, n = _recs(recs)
+        an = np.ascontiguousarray(anchors if anchors is not None else [], dtype=np.int64).reshape(-1); na = int(an.size)
+        ok = (ctypes.c_ubyte * max(1, n))(); of = (ctypes.c_int32 * max(1, n))(*([-7] * max(1, n))); size = ctypes.c_longlong(-7); tsize = ctypes.c_longlong(-7); self.L.verifyBlockTree.restype = ctypes.c_int
+        rc = self.L.verifyBlockTree(_cache_handle(cache), ptr, n, ctypes.c_void_p(tree) if tree else None, an.ctypes.data_as(ctypes.c_void_p) if na else None, na, ctypes.c_void_p(s) if s else None,
+                                    int(bool(commit)), ok, of, ctypes.byref(size), ctypes.byref(tsize))
+        return rc, [bool(ok[i]) for i in range(n)], [int(of[i]) for i in range(n)], (None if size.value == -7 else int(size.value)), (None if tsize.value < 0 else int(tsize.value))   # (no tree: the call writes -1)
     def VerifyDepositProofDepth(self, depth, proof, RT, pk, cmtb_old, sn_old, cmtb, sns):
         return bool(self.L.verifyDepositproofDepth(int(depth), proof.encode(), self.hx(RT), self.hx(pk), self.hx(cmtb_old), self.hx(sn_old), self.hx(cmtb), self.hx(sns)))

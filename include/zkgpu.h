@@ -231,6 +231,11 @@ int zkgpu_tree_paths_at(zkgpu_tree *t, uint64_t size, const uint64_t *indices, s
 int zkgpu_tree_find_at(zkgpu_tree *t, uint64_t size, const uint8_t leaf[32], uint64_t *index);   /* the first of the first `size` leaves holding the blob */
 int zkgpu_tree_rewind(zkgpu_tree *t, uint64_t size);                        /* the tree becomes state `size`: the leaves from `size` on are gone */
 int zkgpu_test_tree_state_launches(zkgpu_tree *t, uint64_t *launches);      /* test entry: kernels launched by the four entries above and by the proofs at a past size */
+/* Anchors (DESIGN.md "A block against the resident tree"; the drop-in level is zk_tree_block.h): match_out[i] = the lowest a with root(sizes[a]) == rts[i], or -1.
+ * rts: n x 32 bytes, in blob order or (hash_order != 0) as the bytes of the common.Hash.  One upload, two launches (zkgpu_tree_roots_at's kernel, then the compare,
+ * both counted by zkgpu_test_tree_state_launches) and n x 4 bytes back; n = 0 or n_sizes = 0 launches nothing, n_sizes = 0 answers -1 everywhere.  ZKGPU_ERR_ARG with
+ * nothing written: a size above the tree's, a null pointer where a count is not 0, n_sizes >= 2^31.  ZKGPU_ERR_NO_DEVICE without a device: there is no host tree. */
+int zkgpu_tree_match_roots(zkgpu_tree *t, const uint64_t *sizes, size_t n_sizes, const uint8_t *rts, size_t n, int hash_order, int32_t *match_out);
 /* test entry, host only: root (if root != NULL) and, if path != NULL, the path of `index` by notes.cpp's tree_levels */
 int zkgpu_test_tree_host(int depth, const uint8_t *leaves, size_t n, uint64_t index, uint8_t root[32], uint8_t *path);
 
