@@ -38,6 +38,7 @@
 #include "../../include/zk_proof_cache.h"
 #include "../../include/zk_spent_pk.h"
 #include "../../include/zk_tree_block.h"
+#include "../../include/zk_tree_chain.h"
 #include "../../include/zkgpu.h"
 #include "blockmaze_circuits.hpp"
 #include "groth16.hpp"
@@ -1521,6 +1522,13 @@ int zkgpu_tree_match_roots(zkgpu_tree *t, const uint64_t *sizes, size_t n_sizes,
   if (n_sizes >= (1ull << 31)) { zkgpu_set_error("commitment tree: 2^31 anchors or more"); return ZKGPU_ERR_ARG; }
   if (!t->t.match_roots(sizes, n_sizes, rts, n, hash_order != 0, match_out)) { zkgpu_set_error("commitment tree: a size above the tree's size"); return ZKGPU_ERR_ARG; }
   return ZKGPU_OK; }); }
+int zkgpu_tree_match_roots_window(zkgpu_tree *t, const uint64_t *sizes, size_t n_sizes, const uint8_t *rts, size_t n, const uint32_t *lo, const uint32_t *hi, int hash_order,
+                                  int32_t *match_out) { return guarded_tree(t, [&] {
+  if ((n_sizes && !sizes) || (n && (!rts || !lo || !hi || !match_out))) { zkgpu_set_error("commitment tree: a null pointer"); return ZKGPU_ERR_ARG; }
+  if (n_sizes >= (1ull << 31)) { zkgpu_set_error("commitment tree: 2^31 anchors or more"); return ZKGPU_ERR_ARG; }
+  if (!t->t.match_roots_window(sizes, n_sizes, rts, n, lo, hi, hash_order != 0, match_out)) {
+    zkgpu_set_error("commitment tree: a size above the tree's size, or a window with lo > hi or hi above the number of anchors"); return ZKGPU_ERR_ARG; }
+  return ZKGPU_OK; }); }
 int zkgpu_test_tree_state_launches(zkgpu_tree *t, uint64_t *launches) { return guarded_tree(t, [&] { if (!launches) return ZKGPU_ERR_ARG; *launches = t->t.state_launches(); return ZKGPU_OK; }); }
 int zkgpu_test_tree_host(int depth, const uint8_t *leaves, size_t n, uint64_t index, uint8_t root[32], uint8_t *path) { return guarded_host([&] {
   if (depth < 1 || depth > 32 || (n && !leaves) || n > (1ull << depth) || (path && index >= n)) return ZKGPU_ERR_ARG;
@@ -1919,6 +1927,93 @@ int verifyBlockTree(zk_proof_cache *cache, const zk_block_record *recs, int n, z
     if (set && set_size_out) *set_size_out = (long long)set_size;
     if (tree_size_out) *tree_size_out = (long long)tree->t.size();
     return accepted;
+  }
+  catch (const std::exception &e) { return fail(e.what()); }
+  catch (...) { return fail("unknown error"); }
+}
+
+// ---- a stretch of the chain (DESIGN.md "A stretch of the chain"; include/zk_tree_chain.h) ----------------------------------------------------------------------
+// The loop "verifyBlockTree(commit = 1) block after block, stop at the first block with a rejected record and take it back" without the loop: every step runs once on
+// the longest prefix of blocks that can still be valid.  B1 >= B2 >= B3 are the first block with a record rejected by the proof step, by the anchor step, by the spend
+// step; blocks < B3 are accepted, block B3's verdicts are already those of the loop (no later record changes an earlier one's verdict), and what was appended or spent
+// beyond block B3 - 1 is rewound.  The tree's, the cache's and the set's mutexes are taken one step after the other, never together.
+int verifyChainTree(zk_proof_cache *cache, const zk_block_record *recs, int n, const int *block_first, int n_blocks, zk_tree *tree, const long long *prior_anchors,
+                    int n_prior, int window, zk_snset *set, unsigned char *ok, int32_t *anchor_of, long long *set_sizes, long long *tree_sizes) {
+  bool appended = false, spent = false; uint64_t size0 = 0, set_before = 0;
+  auto fail = [&](const std::string &why) {
+    zkgpu_set_error(why); fprintf(stderr, "libzkgpu: verifyChainTree: %s\n", why.c_str());
+    if (spent) { try { if (!set->s.rewind(set_before)) throw GpuError("it holds fewer keys than before the call"); } catch (const std::exception &e) { fprintf(stderr, "libzkgpu: verifyChainTree: the spent set could not be rewound (%s)\n", e.what()); } }
+    if (appended) { try { if (!tree->t.rewind(size0)) throw GpuError("it holds fewer leaves than before the call"); } catch (const std::exception &e) { fprintf(stderr, "libzkgpu: verifyChainTree: the tree could not be rewound (%s)\n", e.what()); } }
+    for (int i = 0; i < n; i++) { if (ok) ok[i] = 0; if (anchor_of) anchor_of[i] = -1; }
+    return -1; };
+  try {
+    // 0. the arguments, before anything is queued
+    if (!tree) return fail("no tree");
+    if (n < 0 || n_blocks < 0 || (n && (!recs || !ok))) return fail("a negative count or a null pointer");
+    if (!block_first || block_first[0] != 0 || block_first[n_blocks] != n) return fail("block_first does not run from 0 to n");
+    for (int b = 0; b < n_blocks; b++) if (block_first[b] > block_first[b + 1]) return fail("block_first decreases at block " + std::to_string(b));
+    if (n_prior < 0 || (n_prior && !prior_anchors)) return fail("a negative number of prior anchors or a null pointer");
+    if (window < 0) return fail("a negative window");
+    if (!gpu_available()) return fail("no HIP device visible; libzkgpu has no CPU fallback");
+    const size_t depth = (size_t)tree->t.depth(); size0 = tree->t.size();
+    for (int a = 0; a < n_prior; a++) if (prior_anchors[a] < 0 || (uint64_t)prior_anchors[a] > size0) return fail("prior anchor " + std::to_string(a) + " is negative or above the tree's size");
+    { uint64_t sends = 0; for (int i = 0; i < n; i++) sends += recs[i].kind == ZK_KIND_SEND;
+      if (sends > (1ull << depth) - size0) return fail("the segment's sends do not fit into the tree"); }
+    for (int i = 0; i < n; i++) if (anchor_of) anchor_of[i] = -1;
+    std::vector<int> blk((size_t)n); for (int b = 0; b < n_blocks; b++) for (int i = block_first[b]; i < block_first[b + 1]; i++) blk[i] = b;
+    auto first_rejected = [&](int end) { for (int i = 0; i < end; i++) if (!ok[i]) return blk[i]; return n_blocks; };   // (end = block_first[B + 1] of a block B with a rejection, or n)
+    auto end_of = [&](int B) { return block_first[B < n_blocks ? B + 1 : n_blocks]; };
+    // 1. the proof step over every record, the deposits under the key of the tree's depth
+    if (n && verify_block_records_cached(cache, recs, n, ok, "verifyChainTree", depth) < 0) return fail(zkgpu_last_error());
+    const int B1 = first_rejected(n);
+    // 2. the append: the cmtS of every send of the blocks < B1, in record order, in one append; s[b] = the tree's size after block b
+    std::vector<uint64_t> s((size_t)B1); std::vector<uint8_t> gathered;
+    { HostSpan span("host.tree_gather"); uint64_t at = size0;
+      for (int b = 0; b < B1; b++) {
+        for (int i = block_first[b]; i < block_first[b + 1]; i++) if (recs[i].kind == ZK_KIND_SEND) { at++; for (int k = 0; k < 32; k++) gathered.push_back(recs[i].args[2][31 - k]); }
+        s[b] = at; } }
+    if (!gathered.empty()) { if (!tree->t.append(gathered.data(), gathered.size() / 32)) return fail("the tree is full: another writer appended during the call"); appended = true; }
+    // 3. the anchor step on the deposits of the blocks <= B1, each with its window of A = prior_anchors | s; the roots of the part of A that some window covers
+    std::vector<int> at; std::vector<uint32_t> lo, hi; gathered.clear(); uint64_t a_lo = UINT64_MAX, a_hi = 0;
+    { HostSpan span("host.tree_gather");
+      for (int i = 0, end = end_of(B1); i < end; i++) if (ok[i] && recs[i].kind == ZK_KIND_DEPOSIT) {
+        const uint64_t h = (uint64_t)n_prior + (uint64_t)blk[i], l = h > (uint64_t)window ? h - (uint64_t)window : 0;
+        at.push_back(i); lo.push_back((uint32_t)l); hi.push_back((uint32_t)h); gathered.insert(gathered.end(), recs[i].args[0], recs[i].args[0] + 32);
+        if (l < h) { a_lo = std::min(a_lo, l); a_hi = std::max(a_hi, h); } } }
+    if (!at.empty()) {
+      if (a_lo > a_hi) a_lo = a_hi = 0;                                                           // (every window is empty)
+      std::vector<uint64_t> sizes((size_t)(a_hi - a_lo)); std::vector<int32_t> match(at.size(), -1);
+      for (uint64_t a = a_lo; a < a_hi; a++) sizes[a - a_lo] = a < (uint64_t)n_prior ? (uint64_t)prior_anchors[a] : s[a - (uint64_t)n_prior];   // (a - n_prior < blk[i] <= B1)
+      for (size_t j = 0; j < at.size(); j++) { if (lo[j] < hi[j]) { lo[j] -= (uint32_t)a_lo; hi[j] -= (uint32_t)a_lo; } else lo[j] = hi[j] = 0; }
+      if (!tree->t.match_roots_window(sizes.data(), sizes.size(), gathered.data(), at.size(), lo.data(), hi.data(), true, match.data())) return fail("an anchor is above the tree's size: the tree was rewound during the call");
+      for (size_t j = 0; j < at.size(); j++) { if (match[j] < 0) ok[at[j]] = 0; else if (anchor_of) anchor_of[at[j]] = match[j] + (int32_t)a_lo; }
+    }
+    const int B2 = first_rejected(end_of(B1));
+    // 4. the spend step over the records of the blocks <= B2; a record rejected above brings no key
+    const int end2 = end_of(B2); uint64_t set_size = 0; std::vector<uint64_t> set_at((size_t)n_blocks);
+    if (set) {
+      set_size = set_before = set->s.size(); spent = true;                                        // (a call that fails leaves the set alone, and a rewind to its own size is nothing)
+      if (end2 && block_spend_pairs(recs, end2, set, 1, ok, set_size, "verifyChainTree") < 0) return fail(zkgpu_last_error());
+    }
+    const int B3 = first_rejected(end2);
+    // 5. the sizes of the set after each accepted block: an accepted record inserts its serial number unless that is the exempt key (which is never inserted), and a
+    //    deposit its pk address.  Then the shrink: what lies beyond block B3 - 1 is taken back.  A segment accepted whole rewinds nothing.
+    if (set) {
+      uint8_t exempt[20]; const bool has_exempt = set->s.exempt_key(exempt); uint64_t at_set = set_before;
+      for (int b = 0; b < B3; b++) {
+        for (int i = block_first[b]; i < block_first[b + 1]; i++) at_set += (!(has_exempt && !memcmp(record_sn(recs[i]) + 12, exempt, 20)) ? 1 : 0) + (recs[i].kind == ZK_KIND_DEPOSIT ? 1 : 0);
+        set_at[b] = at_set; }
+      if (at_set > set_size || (B3 == n_blocks && at_set != set_size)) return fail("the spent set's size after the call is not what the accepted records account for");
+      if (at_set != set_size) { if (!set->s.rewind(at_set)) return fail("the spent set could not be rewound to the end of block " + std::to_string(B3 - 1)); set_size = at_set; }
+    }
+    const uint64_t tree_size = B3 ? s[B3 - 1] : size0;
+    if (tree_size != (B1 ? s[B1 - 1] : size0) && !tree->t.rewind(tree_size)) return fail("the tree could not be rewound to the end of block " + std::to_string(B3 - 1));
+    // 6. the verdicts: block B3's are those of the loop already; the blocks after it are not decided
+    for (int i = end_of(B3); i < n; i++) { ok[i] = 0; if (anchor_of) anchor_of[i] = -1; }
+    for (int b = 0; b < n_blocks; b++) {
+      if (set && set_sizes) set_sizes[b] = (long long)(b < B3 ? set_at[b] : set_size);
+      if (tree_sizes) tree_sizes[b] = (long long)(b < B3 ? s[b] : tree_size); }
+    return B3;
   }
   catch (const std::exception &e) { return fail(e.what()); }
   catch (...) { return fail("unknown error"); }

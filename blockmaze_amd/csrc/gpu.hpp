@@ -193,6 +193,9 @@ class CommitmentTree {
   // (hash_order) as the bytes of the common.Hash.  One upload, two launches — roots_at's kernel, then the compare, which reads the roots from device memory — and
   // q x 4 bytes back; q = 0 or m = 0 launches nothing (m = 0: all -1).  false also for m >= 2^31.
   bool match_roots(const uint64_t *sizes, size_t m, const uint8_t *rts, size_t q, bool hash_order, int32_t *match_out);
+  // match_roots with a window a record (DESIGN.md "A stretch of the chain"): only anchors a with lo[i] <= a < hi[i] count for record i, and a workgroup loads only
+  // the roots its records' windows cover.  The same upload (with lo and hi behind the RTs), launches and download.  false also for lo[i] > hi[i] or hi[i] > m.
+  bool match_roots_window(const uint64_t *sizes, size_t m, const uint8_t *rts, size_t q, const uint32_t *lo, const uint32_t *hi, bool hash_order, int32_t *match_out);
   bool paths_at(uint64_t size, const uint64_t *indices, size_t q, uint8_t *siblings /* q x depth x 32 */, uint8_t *root /* 32, or null */);
   bool find_at(uint64_t size, const uint8_t leaf[32], uint64_t &index);                           // the first of the first `size` leaves equal to the blob
   bool snapshot_at(uint64_t size, const uint8_t leaf[32], Snapshot &out);                          // snapshot() of state `size`; false also if the tree is smaller
@@ -210,6 +213,7 @@ class SpentSet {
   explicit SpentSet(const uint8_t *exempt /* 20 bytes, or null */, int log2_slots = 0 /* tests: a table of 2^4 slots or more; 0 = 2^10 */, const uint64_t *seed = nullptr /* tests; null = getrandom */);
   ~SpentSet();
   uint64_t size() const;
+  bool exempt_key(uint8_t out[20]) const;                                     // false: the set has none (out is left alone)
   // the reference's check-then-insert loop in record order (keys: n x 20 bytes; mask: n bytes or null = all in): conflict[i] = 0 skipped (masked out, exempt) or
   // fresh, 1 the key was in the set before the call, 2 an earlier masked-in record of the call has it.  commit: the fresh keys are appended in record order;
   // otherwise the set is afterwards what it was, bit for bit.  One upload, at most one rebuild, three launches and one download whatever n is.

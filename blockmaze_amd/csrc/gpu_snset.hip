@@ -343,6 +343,7 @@ SpentSet::SpentSet(const uint8_t *exempt, int log2_slots, const uint64_t *seed) 
 }
 SpentSet::~SpentSet() { try { LaneScope lane(0); std::lock_guard<std::mutex> gl(g_gpu_mutex); impl.reset(); } catch (...) {} }
 uint64_t SpentSet::size() const { std::lock_guard<std::mutex> lk(impl->mu); return impl->n; }
+bool SpentSet::exempt_key(uint8_t out[20]) const { if (impl->has_exempt) memcpy(out, impl->exempt, 20); return impl->has_exempt; }   // (set once, by the constructor)
 
 // One upload, at most one rebuild, three launches and one download, whatever n is.
 bool SpentSet::spend(const uint8_t *keys, const uint8_t *mask, size_t n, bool commit, uint8_t *conflict, uint64_t *size_out) {

@@ -203,6 +203,64 @@ __global__ void __launch_bounds__(MATCH_THREADS) k_tree_match_roots(const uint32
   }
   if (live) match[t] = best;
 }
+// k_tree_match_roots with a window a record (DESIGN.md "A stretch of the chain"): match[t] = the lowest a with lo[t] <= a < hi[t] and roots[a] == RT t, or -1.  The
+// host has checked lo[t] <= hi[t] <= m.  Records come in block order, so the windows of one workgroup lie close together: the workgroup reduces min lo and max hi
+// over its live lanes with a window that is not empty — inside a wave by shuffles, across the four waves through LDS, one barrier — and loads tiles only from
+// floor(min lo / 8) * 8 up to max hi.  Both bounds are the same in every lane (made scalar below), so a lane at or beyond q, or one with an empty window, still
+// reaches every barrier; a workgroup whose windows are all empty loads nothing.  A tile starts at a multiple of 8, so the steps of eight stay aligned with the
+// tile; a lane starts at the step that holds its lo and skips what lies below lo or at and beyond hi.  Word 0 first, eight LDS reads a step, lowest index wins.
+__global__ void __launch_bounds__(MATCH_THREADS) k_tree_match_roots_window(const uint32_t *__restrict__ roots, const uint32_t *__restrict__ rts, uint64_t q, const uint32_t *__restrict__ lo,
+                                                                           const uint32_t *__restrict__ hi, int hash_order, int32_t *__restrict__ match) {
+  __shared__ uint32_t tile[8 * MATCH_TILE]; __shared__ uint32_t ends[2 * (MATCH_THREADS / 64)];
+  const uint32_t tid = threadIdx.x; const uint64_t t = (uint64_t)blockIdx.x * MATCH_THREADS + tid; const bool live = t < q;
+  uint32_t r[8], my_lo = 0, my_hi = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) r[i] = 0;
+  if (live) {
+    uint32_t w[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) w[i] = rts[8 * t + i];
+#pragma unroll
+    for (int i = 0; i < 8; i++) r[i] = hash_order ? __builtin_bswap32(w[7 - i]) : w[i];
+    my_lo = lo[t]; my_hi = hi[t];
+  }
+  const bool any = my_lo < my_hi;                                                                 // (false for a lane at or beyond q)
+  uint32_t w_lo = any ? my_lo : 0xffffffffu, w_hi = any ? my_hi : 0u;
+#pragma unroll
+  for (int off = 32; off; off >>= 1) { const uint32_t a = __shfl_xor(w_lo, off), b = __shfl_xor(w_hi, off); w_lo = a < w_lo ? a : w_lo; w_hi = b > w_hi ? b : w_hi; }
+  if ((tid & 63) == 0) { ends[tid >> 6] = w_lo; ends[MATCH_THREADS / 64 + (tid >> 6)] = w_hi; }
+  __syncthreads();
+  uint32_t g_lo = 0xffffffffu, g_hi = 0;
+#pragma unroll
+  for (int v = 0; v < MATCH_THREADS / 64; v++) { const uint32_t a = ends[v], b = ends[MATCH_THREADS / 64 + v]; g_lo = a < g_lo ? a : g_lo; g_hi = b > g_hi ? b : g_hi; }
+  g_lo = __builtin_amdgcn_readfirstlane(g_lo); g_hi = __builtin_amdgcn_readfirstlane(g_hi);     // (every lane read the same eight words)
+  int32_t best = -1;
+#pragma unroll 1
+  for (uint32_t base = g_lo < g_hi ? g_lo & ~7u : g_hi; base < g_hi; base += MATCH_TILE) {
+    const uint32_t cnt = g_hi - base < (uint32_t)MATCH_TILE ? g_hi - base : (uint32_t)MATCH_TILE;  // (uniform; base + cnt <= max hi <= m: the loads stay inside roots)
+    __syncthreads();                                                                            // the tile before this one has been read by everyone
+    for (uint32_t i = tid; i < 8 * cnt; i += MATCH_THREADS) tile[i] = roots[8 * (uint64_t)base + i];
+    __syncthreads();
+    if (any && best < 0 && my_lo < base + cnt && my_hi > base) {
+      const uint32_t a0 = my_lo > base ? (my_lo - base) & ~7u : 0u, a1 = my_hi - base < cnt ? my_hi - base : cnt;   // this lane's anchors of the tile: [max(a0, lo - base), a1)
+#pragma unroll 1
+      for (uint32_t a = a0; a < a1 && best < 0; a += 8) {
+        uint32_t w0[8];
+#pragma unroll
+        for (int j = 0; j < 8; j++) w0[j] = tile[8 * (a + j)];                                    // (a is a multiple of 8 below 256: a + j stays inside the tile)
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+          if (best >= 0 || base + a + j < my_lo || a + j >= a1 || w0[j] != r[0]) continue;
+          bool same = true;
+#pragma unroll
+          for (int i = 1; i < 8; i++) same &= tile[8 * (a + j) + i] == r[i];
+          if (same) best = (int32_t)(base + a + j);
+        }
+      }
+    }
+  }
+  if (live) match[t] = best;
+}
 
 struct CommitmentTree::Impl {
   std::mutex mu; uint32_t depth = 0, cap_log = 0; uint64_t n = 0; DevBuf<uint8_t> nodes, empty, out, first /* k_tree_find's word */; std::vector<uint8_t> empty_host;
@@ -336,6 +394,27 @@ bool CommitmentTree::match_roots(const uint64_t *sizes, size_t m, const uint8_t 
   hipLaunchKernelGGL(k_tree_roots_at, dim3((unsigned)cdiv(m, 64)), dim3(64), 0, s, d.geom(), (const unsigned long long *)d.q_in.get(), (uint64_t)m, d.q_out.get()); d.state_launches++;
   hipLaunchKernelGGL(k_tree_match_roots, dim3((unsigned)cdiv(q, MATCH_THREADS)), dim3(MATCH_THREADS), 0, s, (const uint32_t *)d.q_out.get(), (uint32_t)m,
                      (const uint32_t *)(d.q_in.get() + 8 * m), (uint64_t)q, hash_order ? 1 : 0, (int32_t *)(d.q_out.get() + 32 * m)); d.state_launches++;
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipMemcpyAsync(h.data(), d.q_out.get() + 32 * m, 4 * q, hipMemcpyDeviceToHost, s)); HIP_CHECK(hipStreamSynchronize(s));
+  memcpy(match_out, h.data(), 4 * q); return true;
+}
+// match_roots with a window a record: one upload [sizes | RTs | lo | hi], the same two launches with k_tree_match_roots_window as the second, q x 4 bytes back.
+// The windows are checked here, under the tree's lock and before anything is queued: the kernel trusts lo <= hi <= m.
+bool CommitmentTree::match_roots_window(const uint64_t *sizes, size_t m, const uint8_t *rts, size_t q, const uint32_t *lo, const uint32_t *hi, bool hash_order, int32_t *match_out) {
+  Impl &d = *impl; std::lock_guard<std::mutex> lk(d.mu);
+  if ((m && !sizes) || (q && (!rts || !lo || !hi || !match_out)) || m >= (1ull << 31)) return false;
+  for (size_t i = 0; i < m; i++) if (sizes[i] > d.n) return false;
+  for (size_t i = 0; i < q; i++) if (lo[i] > hi[i] || hi[i] > m) return false;
+  if (!q) return true;
+  if (!m) { for (size_t i = 0; i < q; i++) match_out[i] = -1; return true; }
+  LaneScope lane(0); std::lock_guard<std::mutex> gl(g_gpu_mutex); hipStream_t s = gpu().stream;
+  const size_t at_rts = 8 * m, at_lo = at_rts + 32 * q, at_hi = at_lo + 4 * q;                   // (8 m and 32 q keep the words aligned)
+  std::vector<uint8_t> up(at_hi + 4 * q); memcpy(up.data(), sizes, 8 * m); memcpy(up.data() + at_rts, rts, 32 * q); memcpy(up.data() + at_lo, lo, 4 * q); memcpy(up.data() + at_hi, hi, 4 * q);
+  d.grow(d.q_in, up.size()); d.grow(d.q_out, 32 * m + 4 * q); std::vector<int32_t> h(q); Impl::SyncAtExit sync;   // (the vectors outlive the synchronise)
+  HIP_CHECK(hipMemcpyAsync(d.q_in.get(), up.data(), up.size(), hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(k_tree_roots_at, dim3((unsigned)cdiv(m, 64)), dim3(64), 0, s, d.geom(), (const unsigned long long *)d.q_in.get(), (uint64_t)m, d.q_out.get()); d.state_launches++;
+  hipLaunchKernelGGL(k_tree_match_roots_window, dim3((unsigned)cdiv(q, MATCH_THREADS)), dim3(MATCH_THREADS), 0, s, (const uint32_t *)d.q_out.get(), (const uint32_t *)(d.q_in.get() + at_rts),
+                     (uint64_t)q, (const uint32_t *)(d.q_in.get() + at_lo), (const uint32_t *)(d.q_in.get() + at_hi), hash_order ? 1 : 0, (int32_t *)(d.q_out.get() + 32 * m)); d.state_launches++;
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(hipMemcpyAsync(h.data(), d.q_out.get() + 32 * m, 4 * q, hipMemcpyDeviceToHost, s)); HIP_CHECK(hipStreamSynchronize(s));
   memcpy(match_out, h.data(), 4 * q); return true;

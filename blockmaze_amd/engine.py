@@ -355,6 +355,13 @@ class Tree:
         _check(lib().zkgpu_tree_match_roots(ctypes.c_void_p(self.h), m.ctypes.data_as(ctypes.c_void_p) if k else None, ctypes.c_size_t(k), bytes(buf) if q else None, ctypes.c_size_t(q), int(bool(hash_order)),
                                             out.ctypes.data_as(ctypes.c_void_p)))
         return [int(x) for x in out[:q]]
+    def match_roots_window(self, sizes, rts, lo, hi, hash_order=False):
+        """match_roots with a window a record: the lowest a with lo[i] <= a < hi[i] and root(sizes[a]) == RT i, or -1; two launches"""
+        m = np.ascontiguousarray(sizes, dtype=np.uint64).reshape(-1); k = int(m.size); buf = rts if isinstance(rts, (bytes, bytearray)) else b"".join(bytes(x) for x in rts); assert len(buf) % 32 == 0
+        q = len(buf) // 32; out = np.full(max(1, q), -7, dtype=np.int32); l = np.ascontiguousarray(lo, dtype=np.uint32).reshape(-1); h = np.ascontiguousarray(hi, dtype=np.uint32).reshape(-1); assert l.size == h.size == q
+        _check(lib().zkgpu_tree_match_roots_window(ctypes.c_void_p(self.h), m.ctypes.data_as(ctypes.c_void_p) if k else None, ctypes.c_size_t(k), bytes(buf) if q else None, ctypes.c_size_t(q),
+                                                   l.ctypes.data_as(ctypes.c_void_p) if q else None, h.ctypes.data_as(ctypes.c_void_p) if q else None, int(bool(hash_order)), out.ctypes.data_as(ctypes.c_void_p)))
+        return [int(x) for x in out[:q]]
     def rewind(self, size):
         """the tree goes back to its first `size` leaves"""
         _check(lib().zkgpu_tree_rewind(ctypes.c_void_p(self.h), ctypes.c_uint64(size)))
@@ -665,5 +672,15 @@ class Zk:
         rc = self.L.verifyBlockTree(_cache_handle(cache), ptr, n, ctypes.c_void_p(tree) if tree else None, an.ctypes.data_as(ctypes.c_void_p) if na else None, na, ctypes.c_void_p(s) if s else None,
                                     int(bool(commit)), ok, of, ctypes.byref(size), ctypes.byref(tsize))
         return rc, [bool(ok[i]) for i in range(n)], [int(of[i]) for i in range(n)], (None if size.value == -7 else int(size.value)), (None if tsize.value < 0 else int(tsize.value))   # (no tree: the call writes -1)
+    # include/zk_tree_chain.h: a stretch of the chain decided against the resident tree
+    def VerifyChainTree(self, cache, items, block_first, tree, prior_anchors, window, s):
+        """block_first: n_blocks + 1 record indices; tree: a handle of TreeNew; prior_anchors: tree sizes; s: a set's handle or None
+        -> (blocks accepted or -1, [bool], [anchor_of], [set size after block b] or None, [tree size after block b] or None)"""
+        recs = items if isinstance(items, np.ndarray) else records_from_items(items); recs, ptr, n = _recs(recs)
+        bf = np.ascontiguousarray(block_first, dtype=np.int32).reshape(-1); nb = int(bf.size) - 1; pa = np.ascontiguousarray(prior_anchors if prior_anchors is not None else [], dtype=np.int64).reshape(-1); npa = int(pa.size)
+        ok = (ctypes.c_ubyte * max(1, n))(); of = (ctypes.c_int32 * max(1, n))(*([-7] * max(1, n))); ss = np.full(max(1, nb), -7, dtype=np.int64); ts = np.full(max(1, nb), -7, dtype=np.int64); self.L.verifyChainTree.restype = ctypes.c_int
+        rc = self.L.verifyChainTree(_cache_handle(cache), ptr, n, bf.ctypes.data_as(ctypes.c_void_p) if nb >= 0 else None, nb, ctypes.c_void_p(tree) if tree else None, pa.ctypes.data_as(ctypes.c_void_p) if npa else None, npa,
+                                    int(window), ctypes.c_void_p(s) if s else None, ok, of, ss.ctypes.data_as(ctypes.c_void_p), ts.ctypes.data_as(ctypes.c_void_p))
+        return (rc, [bool(ok[i]) for i in range(n)], [int(of[i]) for i in range(n)], ([int(x) for x in ss[:nb]] if rc >= 0 and s else None), ([int(x) for x in ts[:nb]] if rc >= 0 else None))
     def VerifyDepositProofDepth(self, depth, proof, RT, pk, cmtb_old, sn_old, cmtb, sns):
         return bool(self.L.verifyDepositproofDepth(int(depth), proof.encode(), self.hx(RT), self.hx(pk), self.hx(cmtb_old), self.hx(sn_old), self.hx(cmtb), self.hx(sns)))

@@ -236,6 +236,12 @@ int zkgpu_test_tree_state_launches(zkgpu_tree *t, uint64_t *launches);      /* t
  * both counted by zkgpu_test_tree_state_launches) and n x 4 bytes back; n = 0 or n_sizes = 0 launches nothing, n_sizes = 0 answers -1 everywhere.  ZKGPU_ERR_ARG with
  * nothing written: a size above the tree's, a null pointer where a count is not 0, n_sizes >= 2^31.  ZKGPU_ERR_NO_DEVICE without a device: there is no host tree. */
 int zkgpu_tree_match_roots(zkgpu_tree *t, const uint64_t *sizes, size_t n_sizes, const uint8_t *rts, size_t n, int hash_order, int32_t *match_out);
+/* Anchors inside a window (DESIGN.md "A stretch of the chain"; the drop-in level is zk_tree_chain.h): match_out[i] = the lowest a with lo[i] <= a < hi[i] and
+ * root(sizes[a]) == rts[i], or -1; lo[i] == hi[i] is an empty window.  Upload, launches, download and counters as zkgpu_tree_match_roots; a workgroup of the compare
+ * loads only the roots that the windows of its 256 records cover, so records whose windows lie close together — a segment in block order — cost what their windows
+ * hold and not n_sizes.  ZKGPU_ERR_ARG with nothing written: as above, and lo[i] > hi[i] or hi[i] > n_sizes.  ZKGPU_ERR_NO_DEVICE without a device. */
+int zkgpu_tree_match_roots_window(zkgpu_tree *t, const uint64_t *sizes, size_t n_sizes, const uint8_t *rts, size_t n, const uint32_t *lo, const uint32_t *hi, int hash_order,
+                                  int32_t *match_out);
 /* test entry, host only: root (if root != NULL) and, if path != NULL, the path of `index` by notes.cpp's tree_levels */
 int zkgpu_test_tree_host(int depth, const uint8_t *leaves, size_t n, uint64_t index, uint8_t root[32], uint8_t *path);
 
