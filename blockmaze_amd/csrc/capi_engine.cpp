@@ -14,6 +14,7 @@ void probe_fq2(int op, const uint8_t *a, const uint8_t *b, uint8_t *out, size_t 
 void probe_group(int group, int op, const uint8_t *a, const uint8_t *b, uint8_t *out, size_t n);
 void probe_field29(int field, int op, const uint32_t *a, const uint32_t *b, const uint32_t *c, const uint32_t *d, uint32_t *out, size_t n);
 void probe_point29(int op, const uint32_t *a, const uint32_t *b, uint32_t *out, uint32_t *flags, size_t n);
+void probe_fq2_sqrt(const uint8_t *a, uint8_t *out, uint8_t *ok, size_t n);   // gpu_keyops.hip, next to fq2_sqrt
 }
 using namespace zk;
 using namespace zk::host;
@@ -53,6 +54,9 @@ static void g2_out(const HG2 &p, uint8_t *o) {
   HFq v[4] = {x.c0.from_mont(), x.c1.from_mont(), y.c0.from_mont(), y.c1.from_mont()};
   for (int k = 0; k < 4; k++) memcpy(o + 32 * k, v[k].l, 32);
 }
+// Montgomery records -> canonical bytes (the point at infinity is all zero either way)
+static void g1_raw_out(const G1AffineRaw &r, uint8_t *o) { const Fe32 *src = &r.x; for (int k = 0; k < 2; k++) { HFq v; memcpy(v.l, &src[k], 32); v = v.from_mont(); memcpy(o + 32 * k, v.l, 32); } }
+static void g2_raw_out(const G2AffineRaw &r, uint8_t *o) { const Fe32 *src = &r.x0; for (int k = 0; k < 4; k++) { HFq v; memcpy(v.l, &src[k], 32); v = v.from_mont(); memcpy(o + 32 * k, v.l, 32); } }
 static int auto_window(size_t n) { int lg = 0; while (((size_t)1 << lg) < n) lg++; int c = lg - 2; if (c < 7) c = 7; if (c > 16) c = 16; return c; }
 
 struct zkgpu_msm { int group; size_t n; std::unique_ptr<MsmG1> g1; std::unique_ptr<MsmG2> g2; DevBuf<Fe32> scalars; };
@@ -72,7 +76,7 @@ int zkgpu_test_field_op(int field, int op, const uint8_t *a, const uint8_t *b, u
   return guarded([&] { probe_field(field, op, a, b, out, n); return ZKGPU_OK; });
 }
 int zkgpu_test_fq2_op(int op, const uint8_t *a, const uint8_t *b, uint8_t *out, size_t n) {
-  return guarded([&] { probe_fq2(op, a, b, out, n); return ZKGPU_OK; });
+  return guarded([&] { if (op == 3) probe_fq2_sqrt(a, out, out + 64 * n, n); else probe_fq2(op, a, b, out, n); return ZKGPU_OK; });
 }
 int zkgpu_test_group_op(int group, int op, const uint8_t *a, const uint8_t *b, uint8_t *out, size_t n) {
   return guarded([&] { probe_group(group, op, a, b, out, n); return ZKGPU_OK; });
@@ -176,4 +180,30 @@ int zkgpu_witness_map(zkgpu_r1cs *cs, const uint8_t *z, uint8_t *h_out) { return
   cs->dom->qap_pointwise(abc.get(), abc.get() + m, abc.get() + 2 * m);
   cs->dom->icoset_fft(abc.get(), 1, m);
   fr_from_mont_dev(abc.get(), m); abc.download((Fe32 *)h_out, m); memset(h_out + 32 * m, 0, 32); return ZKGPU_OK; }); }
+
+// ---- test entries of the key-side operations: the host functions key generation and key load call, unchanged, on caller arrays ----
+int zkgpu_test_decompress(int group, const uint8_t *xs_mont, const uint8_t *flags, size_t n, uint8_t *points_out) {
+  return guarded([&] { if (group != 1 && group != 2) { g_err = "group must be 1 or 2"; return ZKGPU_ERR_ARG; }
+    if (group == 1) { std::vector<G1AffineRaw> p(n ? n : 1); decompress_g1((const Fe32 *)xs_mont, flags, n, p.data()); for (size_t i = 0; i < n; i++) g1_raw_out(p[i], points_out + 64 * i); }
+    else { std::vector<G2AffineRaw> p(n ? n : 1); decompress_g2((const Fe32 *)xs_mont, flags, n, p.data()); for (size_t i = 0; i < n; i++) g2_raw_out(p[i], points_out + 128 * i); }
+    return ZKGPU_OK; });
+}
+int zkgpu_test_fixed_base_mul(int group, const uint8_t *base, const uint8_t *scalars, size_t n, uint8_t *points_out) {
+  return guarded([&] { if (group != 1 && group != 2) { g_err = "group must be 1 or 2"; return ZKGPU_ERR_ARG; }
+    if (group == 1) { G1AffineRaw b; g1_to_raw(base, b); HFq x, y; memcpy(x.l, &b.x, 32); memcpy(y.l, &b.y, 32);
+      std::vector<G1AffineRaw> p(n ? n : 1); fixed_base_mul_g1(HG1::from_affine(x, y), (const Fe32 *)scalars, n, p.data()); for (size_t i = 0; i < n; i++) g1_raw_out(p[i], points_out + 64 * i); }
+    else { G2AffineRaw b; g2_to_raw(base, b); HFq2 x, y; memcpy(x.c0.l, &b.x0, 32); memcpy(x.c1.l, &b.x1, 32); memcpy(y.c0.l, &b.y0, 32); memcpy(y.c1.l, &b.y1, 32);
+      std::vector<G2AffineRaw> p(n ? n : 1); fixed_base_mul_g2(HG2::from_affine(x, y), (const Fe32 *)scalars, n, p.data()); for (size_t i = 0; i < n; i++) g2_raw_out(p[i], points_out + 128 * i); }
+    return ZKGPU_OK; });
+}
+int zkgpu_test_h_query_lagrange(size_t min_size, const uint8_t *h, size_t n_in, uint8_t *out) {
+  return guarded([&] { Domain d(min_size); const size_t m = d.m(); if (n_in > m) { g_err = "n_in exceeds the domain"; return ZKGPU_ERR_ARG; }
+    std::vector<G1AffineRaw> in(n_in ? n_in : 1), res(m); for (size_t i = 0; i < n_in; i++) g1_to_raw(h + 64 * i, in[i]);
+    d.h_query_to_coset_lagrange(in.data(), n_in, res.data()); for (size_t j = 0; j < m; j++) g1_raw_out(res[j], out + 64 * j); return ZKGPU_OK; });
+}
+int zkgpu_test_fold_c(zkgpu_r1cs *cs, const uint8_t *h_lagrange, const uint8_t *L, uint8_t *out) {
+  return guarded([&] { if (!cs) return ZKGPU_ERR_ARG; const size_t m = cs->dom->m(), nl = cs->host.n_vars - cs->host.n_inputs, n_all = cs->host.n_vars + 1;
+    std::vector<G1AffineRaw> p(m), l(nl ? nl : 1), res(n_all); for (size_t j = 0; j < m; j++) g1_to_raw(h_lagrange + 64 * j, p[j]); for (size_t i = 0; i < nl; i++) g1_to_raw(L + 64 * i, l[i]);
+    cs->dom->fold_c_into_l(p.data(), cs->host, l.data(), res.data()); for (size_t v = 0; v < n_all; v++) g1_raw_out(res[v], out + 64 * v); return ZKGPU_OK; });
+}
 }  // extern "C"

@@ -10,6 +10,8 @@ namespace zk {
 // r1cs_gg_ppzksnark.tcc:466-473).  h_i = (g^-i / m) sum_j v_j w^(-ij), hence  sum_i h_i H_i = sum_j v_j P_j  with  P_j = sum_i w^(-ij) * ((g^-i / m) H_i):
 // the inverse DFT, over GROUP ELEMENTS, of the scaled query (H_(m-1) := 0, its coefficient is zero anyway).  Computing P once per key (m/2 * log m point
 // multiplications by twiddles) removes the seventh transform from every proof; the group element, and so the proof bytes, are the same.
+// bit reversal of p < 2^logm; logm = 0 is the small part of the step domains 2^k + 1, where a shift by 32 - logm would be undefined
+__device__ __forceinline__ uint32_t ecntt_bitrev(uint32_t p, int logm) { return logm ? __brev(p) >> (32 - logm) : 0u; }
 // k * p, MSB-first double-and-add over the canonical bits of k
 template <class F> __device__ __forceinline__ XYZZ<F> xyzz_mul_fr(const XYZZ<F> &p, const Fr &k_mont) {
   const Fr k = k_mont.from_mont(); XYZZ<F> r = XYZZ<F>::inf(); bool started = false;
@@ -59,7 +61,7 @@ __global__ void __launch_bounds__(64) k_ecntt_step_pre(const XYZZ<Fq> *__restric
 // out[bitrev(p)] = affine(data[p])
 // (data / out already offset to the sub-transform)
 __global__ void __launch_bounds__(64) k_ecntt_finish(const XYZZ<Fq> *__restrict__ data, int logm, Affine<Fq> *__restrict__ out) {
-  uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; if (p >= (1u << logm)) return; const XYZZ<Fq> q = data[p]; const uint32_t r = __brev(p) >> (32 - logm);
+  uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; if (p >= (1u << logm)) return; const XYZZ<Fq> q = data[p]; const uint32_t r = ecntt_bitrev(p, logm);
   if (q.is_inf()) { out[r] = Affine<Fq>::inf(); return; }
   Fq t = (q.ZZ * q.ZZZ).inv(); out[r] = {q.X * (t * q.ZZZ), q.Y * (t * q.ZZ)};
 }
@@ -93,7 +95,7 @@ __global__ void __launch_bounds__(64) k_ecntt_permute_scale(const XYZZ<Fq> *__re
     XYZZ<Fq> *__restrict__ out) {
   uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= (1u << logm)) return;
-  const uint32_t r = __brev(p) >> (32 - logm);
+  const uint32_t r = ecntt_bitrev(p, logm);
   out[r] = xyzz_mul_fr(in[p], scale[r]);
 }
 // Step domains: the forward transform is  (DFT_B (+) DFT_S) . Pre  with  c[i] = a[i] + [i<S] a[i+B],  d[t] = w^t (a[t] - [t<S] a[t+B]),  e[i] = sum_j d[i + jS]
@@ -103,7 +105,7 @@ __global__ void __launch_bounds__(64) k_ecntt_permute_scale(const XYZZ<Fq> *__re
 __global__ void __launch_bounds__(64) k_ecntt_step_fwd_T(const XYZZ<Fq> *__restrict__ Cb, const XYZZ<Fq> *__restrict__ Eb, int logB, int logS,
     const Fr *__restrict__ wpow, const Fr *__restrict__ gpow, XYZZ<Fq> *__restrict__ T) {
   const uint32_t B = 1u << logB, S = 1u << logS; uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; if (t >= B) return;
-  const XYZZ<Fq> c = Cb[__brev(t) >> (32 - logB)]; XYZZ<Fq> we = xyzz_mul_fr(Eb[__brev(t % S) >> (32 - logS)], wpow[t]);
+  const XYZZ<Fq> c = Cb[ecntt_bitrev(t, logB)]; XYZZ<Fq> we = xyzz_mul_fr(Eb[ecntt_bitrev(t % S, logS)], wpow[t]);
   XYZZ<Fq> lo = c; lo.add_inl(we); T[t] = xyzz_mul_fr(lo, gpow[t]);
   if (t < S) { XYZZ<Fq> hi = c; hi.add_inl(we.neg()); T[B + t] = xyzz_mul_fr(hi, gpow[B + t]); }
 }
@@ -114,7 +116,7 @@ __global__ void __launch_bounds__(64) k_ecntt_scale_table(const Affine<Fq> *__re
 }
 // natural-order copy of a bit-reversed array
 __global__ void __launch_bounds__(64) k_ecntt_unpermute(const XYZZ<Fq> *__restrict__ in, int logm, XYZZ<Fq> *__restrict__ out) {
-  uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; if (p >= (1u << logm)) return; out[__brev(p) >> (32 - logm)] = in[p];
+  uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; if (p >= (1u << logm)) return; out[ecntt_bitrev(p, logm)] = in[p];
 }
 // Lstar[v] = (v > n_inputs ? L[v - n_inputs - 1] : 0) - sum over the entries (k, coefficient) of column v of C of coefficient * U[k]; U is held bit-reversed.
 // kind[e]: 0 = +1, 1 = -1, 2 = general (coef[e], canonical)
@@ -124,7 +126,7 @@ __global__ void __launch_bounds__(64) k_fold_c_columns(const uint32_t *__restric
                                                            const Affine<Fq> *__restrict__ L, uint32_t n_inputs, uint32_t n_all, Affine<Fq> *__restrict__ out) {
   uint32_t v = blockIdx.x * blockDim.x + threadIdx.x; if (v >= n_all) return; XYZZ<Fq> acc = XYZZ<Fq>::inf();
 #pragma unroll 1
-  for (uint32_t e = colptr[v]; e < colptr[v + 1]; e++) { XYZZ<Fq> u = U_bitrev[logm ? __brev(rowidx[e]) >> (32 - logm) : rowidx[e]]; uint8_t kd = kind[e];
+  for (uint32_t e = colptr[v]; e < colptr[v + 1]; e++) { XYZZ<Fq> u = U_bitrev[logm ? ecntt_bitrev(rowidx[e], logm) : rowidx[e]]; uint8_t kd = kind[e];
     if (kd == 2) u = xyzz_mul_canon(u, coef[e]); else if (kd == 1) u = u.neg(); acc.add_inl(u); }
   acc = acc.neg(); if (v > n_inputs) acc.madd_inl(L[v - n_inputs - 1]);
   if (acc.is_inf()) { out[v] = Affine<Fq>::inf(); return; }

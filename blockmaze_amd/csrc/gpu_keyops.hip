@@ -91,4 +91,17 @@ void fixed_base_mul_g2(const host::HG2 &base, const Fe32 *scalars, size_t n, G2A
   fixed_base_mul<host::HFq2, Fq2, G2AffineRaw>(base, scalars, n, out);
 }
 
+// test probe (zkgpu_test_fq2_op, op 3): fq2_sqrt on canonical elements; out[i] = the root (canonical, zero where there is none), ok[i] = fq2_sqrt's verdict
+__global__ void k_probe_fq2_sqrt(const Fq2 *__restrict__ a, Fq2 *__restrict__ out, uint8_t *__restrict__ ok, uint32_t n, FqPowConsts pc) {
+  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; if (i >= n) return;
+  Fq2 x = {a[i].c0.to_mont(), a[i].c1.to_mont()}, r = Fq2::zero(); const bool good = fq2_sqrt(x, r, pc); if (!good) r = Fq2::zero();
+  out[i] = {r.c0.from_mont(), r.c1.from_mont()}; ok[i] = good ? 1 : 0;
+}
+void probe_fq2_sqrt(const uint8_t *a, uint8_t *out, uint8_t *ok, size_t n) {
+  if (!n) return;
+  DevBuf<Fe32> da(2 * n), dout(2 * n); DevBuf<uint8_t> dok(n); da.upload((const Fe32 *)a, 2 * n);
+  hipLaunchKernelGGL(k_probe_fq2_sqrt, dim3(cdiv(n, 64)), dim3(64), 0, gpu().stream, (const Fq2 *)da.get(), (Fq2 *)dout.get(), dok.get(), (uint32_t)n, fq_pow_consts());
+  HIP_CHECK(hipGetLastError()); dout.download((Fe32 *)out, 2 * n); dok.download(ok, n);
+}
+
 }  // namespace zk

@@ -47,6 +47,10 @@ def fq2_op(op, a, b=None):
     a = np.ascontiguousarray(a, dtype=np.uint64); out = np.zeros_like(a); n = a.size // 8
     bb = np.ascontiguousarray(b, dtype=np.uint64) if b is not None else None
     _check(lib().zkgpu_test_fq2_op({"mul": 0, "sqr": 1, "inv": 2}[op], _bytes(a), _bytes(bb) if bb is not None else None, _bytes(out), ctypes.c_size_t(n))); return out
+def fq2_sqrt(a):
+    """key load's fq2_sqrt (keyops.cuh) on (n, 8) words: (roots (n, 8), ok (n,) uint8); a root is zero where ok is 0"""
+    a = np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, 8); n = a.shape[0]; buf = np.zeros(65 * n, dtype=np.uint8)
+    _check(lib().zkgpu_test_fq2_op(3, _bytes(a), None, _bytes(buf), ctypes.c_size_t(n))); return buf[:64 * n].copy().view(np.uint64).reshape(n, 8), buf[64 * n:].copy()
 def group_op(group, op, a, b=None):
     """group 1: (n,8) words, group 2: (n,16) words.  op: add / dbl / madd / mul_small (b = uint32 multipliers)"""
     a = np.ascontiguousarray(a, dtype=np.uint64); out = np.zeros_like(a); n = a.shape[0]
@@ -113,11 +117,29 @@ class R1cs:
     def witness_map(self, z):
         z = np.ascontiguousarray(z, dtype=np.uint64); H = np.zeros((self.m + 1, 4), dtype=np.uint64)
         _check(lib().zkgpu_witness_map(ctypes.c_void_p(self.h), _bytes(z), _bytes(H))); return H
+    def fold_c(self, h_lagrange, L):
+        """test entry: h_lagrange (m, 8), L (n_vars - n_inputs, 8) words -> the folded L query, (n_vars + 1, 8)"""
+        P = np.ascontiguousarray(h_lagrange, dtype=np.uint64); L = np.ascontiguousarray(L, dtype=np.uint64); assert P.size == 8 * self.m and L.size == 8 * (self.n_vars - self.n_inputs)
+        out = np.zeros((self.n_vars + 1, 8), dtype=np.uint64); _check(lib().zkgpu_test_fold_c(ctypes.c_void_p(self.h), _bytes(P), _bytes(L), _bytes(out))); return out
     def close(self):
         if self.h: lib().zkgpu_r1cs_destroy(ctypes.c_void_p(self.h)); self.h = None
     def __del__(self):
         try: self.close()
         except Exception: pass
+
+# ---- key-side operations on caller arrays (test entries): points (n, 8) / (n, 16) words, canonical ----
+def decompress(group, xs_mont, flags):
+    """xs_mont: (n, 4) words for G1, (n, 8) for G2, Montgomery form; flags: n bytes (bit 0 lsb of y / y.c0, bit 1 infinity).  Raises if an x is on no point."""
+    w = 4 * group; xs = np.ascontiguousarray(xs_mont, dtype=np.uint64).reshape(-1, w); n = xs.shape[0]; f = np.ascontiguousarray(flags, dtype=np.uint8); assert f.shape == (n,)
+    out = np.zeros((n, 8 * group), dtype=np.uint64); _check(lib().zkgpu_test_decompress(int(group), _bytes(xs), _bytes(f), ctypes.c_size_t(n), _bytes(out))); return out
+def fixed_base_mul(group, base, scalars):
+    """base: 8 / 16 words (affine), scalars: (n, 4) words canonical -> scalars[i] * base"""
+    b = np.ascontiguousarray(base, dtype=np.uint64).reshape(8 * group); k = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4); n = k.shape[0]
+    out = np.zeros((n, 8 * group), dtype=np.uint64); _check(lib().zkgpu_test_fixed_base_mul(int(group), _bytes(b), _bytes(k), ctypes.c_size_t(n), _bytes(out))); return out
+def h_query_lagrange(min_size, h):
+    """h: (n_in, 8) words, n_in <= m -> the m points of the H query in the coset's Lagrange basis"""
+    h = np.ascontiguousarray(h, dtype=np.uint64).reshape(-1, 8); out = np.zeros((domain_size(min_size), 8), dtype=np.uint64)
+    _check(lib().zkgpu_test_h_query_lagrange(ctypes.c_size_t(min_size), _bytes(h), ctypes.c_size_t(h.shape[0]), _bytes(out))); return out
 
 # ---- circuits, keys, prover, verifier ---------------------------------------------------------------------------------
 KIND = {"mint": 0, "send": 1, "deposit": 2, "redeem": 3, "sha256": 100, "merkle": 101, "lesscmp": 102, "cmta": 103, "cmts": 104, "prf": 105, "crh": 106, "unpacker": 107}

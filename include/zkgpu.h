@@ -43,7 +43,8 @@ int zkgpu_init(void);                               /* create the device context
 /* field: 0 = Fr, 1 = Fq.  op: 0 mul, 1 add, 2 sub, 3 inverse(a), 4 square(a), 5 negate(a) */
 int zkgpu_test_field_op(int field, int op, const uint8_t *a, const uint8_t *b, uint8_t *out, size_t n);
 /* (field ops 6..9 probe the lazy domain of field.cuh: 6 mul, 7 square, 8 sub on operands pushed towards 2p, 9 masked negation; results normalized) */
-/* op: 0 mul, 1 square(a), 2 inverse(a) on Fq2 (64-byte elements c0 | c1) */
+/* op: 0 mul, 1 square(a), 2 inverse(a) on Fq2 (64-byte elements c0 | c1); 3 square root by key load's fq2_sqrt (keyops.cuh): out = n roots (zero where a is no
+   square) followed by n bytes, fq2_sqrt's verdict (1 = a is a square) */
 int zkgpu_test_fq2_op(int op, const uint8_t *a, const uint8_t *b, uint8_t *out, size_t n);
 /* group: 1 = G1, 2 = G2.  op: 0 general add, 1 double(a), 2 mixed add (b affine), 3 a*k for 32-bit k (k in b's first 4 bytes) */
 int zkgpu_test_group_op(int group, int op, const uint8_t *a, const uint8_t *b, uint8_t *out, size_t n);
@@ -87,6 +88,19 @@ zkgpu_r1cs *zkgpu_r1cs_create(size_t n_inputs, size_t n_vars, size_t n_cons, con
 void zkgpu_r1cs_destroy(zkgpu_r1cs *cs);
 /* z: n_vars elements (without ONE).  h_out: (m+1) elements, m = zkgpu_domain_size(n_cons + n_inputs + 1).  Returns ZKGPU_ERR_UNSATISFIED if z violates a constraint. */
 int zkgpu_witness_map(zkgpu_r1cs *cs, const uint8_t *z, uint8_t *h_out);
+
+/* ---- key-side operations (test entries): the host functions of key generation and key load, unchanged, on caller arrays.  Points canonical as everywhere here.
+ * zkgpu_test_decompress (group 1 / 2; decompress_g1 / _g2 as groth16_keyio.cpp calls them): xs_mont = n x-coordinates in MONTGOMERY form (32 bytes for G1, c0 | c1 = 64 for
+ *   G2), flags: bit 0 = the lsb of canonical y (y.c0 for G2), bit 1 = the point at infinity; points_out: n points.  An x that is on no point is ZKGPU_ERR_RUNTIME, no points.
+ * zkgpu_test_fixed_base_mul (fixed_base_mul_g1 / _g2, key generation's window tables): points_out[i] = scalars[i] * base, base affine, scalars canonical.
+ * zkgpu_test_h_query_lagrange (Domain::h_query_to_coset_lagrange, ecntt.cuh): h = n_in <= m points (infinity allowed), out = the m points P_j of the domain of
+ *   zkgpu_domain_size(min_size) with sum_j v_j P_j = sum_i icosetFFT(v)_i h_i for every v.
+ * zkgpu_test_fold_c (Domain::fold_c_into_l on the domain of cs): h_lagrange = m points, L = n_vars - n_inputs points, out = n_vars + 1 points, the L query extended to all
+ *   variables minus the C polynomial's share of the H term. */
+int zkgpu_test_decompress(int group, const uint8_t *xs_mont, const uint8_t *flags, size_t n, uint8_t *points_out);
+int zkgpu_test_fixed_base_mul(int group, const uint8_t *base, const uint8_t *scalars, size_t n, uint8_t *points_out);
+int zkgpu_test_h_query_lagrange(size_t min_size, const uint8_t *h, size_t n_in, uint8_t *out);
+int zkgpu_test_fold_c(zkgpu_r1cs *cs, const uint8_t *h_lagrange, const uint8_t *L, uint8_t *out);
 
 /* ---- circuits, keys, resident prover, verifier -------------------------------------------------------------------- */
 /* kind: 0 mint, 1 send, 2 deposit, 3 redeem (100 / 101 / 102 / 103 = test circuits: libsnark's sha256 two-to-one, Merkle check-read, BlockMaze's less-comparison block, one sha256_CMTA_gadget; 104..106 the CMTS / PRF / CRH blocks; 107 the public-input unpacker over tree_depth bits).  tree_depth only matters for deposit (reference: 8) and kind 107. */

@@ -169,7 +169,7 @@ def test_msm_linearity_at_scale():
     K3 = o.to_arr([(a + b) % o.R_MOD for a, b in zip(k1, k2)]); assert run(K3) == o.g1_op("add", r1, r2)
     m.close()
 
-@pytest.mark.parametrize("m", [2, 4, 16, 24, 48, 64, 80, 1024, 1536, 2048, 4096, 5120, 1 << 13, (1 << 14) + (1 << 12), 1 << 16])
+@pytest.mark.parametrize("m", [2, 3, 5, 6, 12, 4, 16, 24, 48, 64, 80, 1024, 1536, 2048, 4096, 5120, 1 << 13, (1 << 14) + (1 << 12), 1 << 16])
 def test_domain_transforms_match_oracle(m):
     assert e.domain_size(m) == o.domain_size(m); a = rand_field_arr(40 + m, o.domain_size(m))
     for op in ("fft", "ifft", "cosetfft", "icosetfft"):
