@@ -7,6 +7,7 @@
 #include <vector>
 #include "../../include/zkgpu.h"
 #include "gpu.hpp"
+#include "capi_accounts.hpp"
 
 namespace zk {
 void probe_field(int field, int op, const uint8_t *a, const uint8_t *b, uint8_t *out, size_t n);
@@ -206,4 +207,60 @@ int zkgpu_test_fold_c(zkgpu_r1cs *cs, const uint8_t *h_lagrange, const uint8_t *
     std::vector<G1AffineRaw> p(m), l(nl ? nl : 1), res(n_all); for (size_t j = 0; j < m; j++) g1_to_raw(h_lagrange + 64 * j, p[j]); for (size_t i = 0; i < nl; i++) g1_to_raw(L + 64 * i, l[i]);
     cs->dom->fold_c_into_l(p.data(), cs->host, l.data(), res.data()); for (size_t v = 0; v < n_all; v++) g1_raw_out(res[v], out + 64 * v); return ZKGPU_OK; });
 }
+}  // extern "C"
+
+// ---- the account table resident in HBM (DESIGN.md "Account table"; include/zkgpu.h) -----------------------------------------------------------------------------
+template <class Fn> static int guarded_accts(zkgpu_accts *a, Fn fn) {
+  try {
+    if (!gpu_available()) { g_err = "no HIP device visible; libzkgpu has no CPU fallback"; return ZKGPU_ERR_NO_DEVICE; }
+    if (!a) { g_err = "no account table"; return ZKGPU_ERR_ARG; }
+    return fn();
+  }
+  catch (const std::exception &e) { g_err = e.what(); return ZKGPU_ERR_RUNTIME; }
+  catch (...) { g_err = "unknown error"; return ZKGPU_ERR_RUNTIME; }
+}
+static zkgpu_accts *accts_create(int log2_slots, const uint64_t *seed) {
+  zkgpu_accts *a = nullptr;
+  try {
+    if (!gpu_available()) { g_err = "no HIP device visible; libzkgpu has no CPU fallback"; return nullptr; }
+    a = new zkgpu_accts(log2_slots, seed);
+  }
+  catch (const std::exception &e) { g_err = e.what(); } catch (...) { g_err = "unknown error"; }
+  return a;
+}
+extern "C" {
+zkgpu_accts *zkgpu_accts_create(void) { return accts_create(0, nullptr); }
+zkgpu_accts *zkgpu_test_accts_create(int log2_slots, uint64_t seed) {
+  if (log2_slots < 4 || log2_slots > 31) { g_err = "account table: a table has 2^4 to 2^31 slots"; return nullptr; }
+  return accts_create(log2_slots, &seed); }
+void zkgpu_accts_destroy(zkgpu_accts *a) { try { delete a; } catch (...) {} }
+int zkgpu_accts_size(zkgpu_accts *a, uint64_t *n) { return guarded_accts(a, [&] { if (!n) return ZKGPU_ERR_ARG; *n = a->a.size(); return ZKGPU_OK; }); }
+int zkgpu_accts_set(zkgpu_accts *a, const uint8_t *addrs, const uint8_t *values, size_t n) { return guarded_accts(a, [&] {
+  if (!a->a.set(addrs, values, n, nullptr)) { g_err = "account table: a null pointer, or the log would reach 2^32 - 2 entries"; return ZKGPU_ERR_ARG; }
+  return ZKGPU_OK; }); }
+int zkgpu_accts_get(zkgpu_accts *a, const uint8_t *addrs, size_t n, int64_t at_size, uint8_t *out) { return guarded_accts(a, [&] {
+  if (!a->a.get(addrs, n, at_size, out)) { g_err = "account table: size " + std::to_string(at_size) + " is above the table's size, or a null pointer"; return ZKGPU_ERR_ARG; }
+  return ZKGPU_OK; }); }
+int zkgpu_accts_fill(zkgpu_accts *a, const uint8_t *addrs, zk_block_record *recs, size_t n, int chained) { return guarded_accts(a, [&] {
+  if (!a->a.fill(addrs, (uint8_t *)recs, n, chained != 0)) { g_err = "account table: a null pointer, or more records than the log has room for"; return ZKGPU_ERR_ARG; }
+  return ZKGPU_OK; }); }
+int zkgpu_accts_commit_chain(zkgpu_accts *a, const uint8_t *addrs, const zk_block_record *recs, size_t n) { return guarded_accts(a, [&] {
+  if (!a->a.commit_chain(addrs, (const uint8_t *)recs, n, nullptr)) { g_err = "account table: a null pointer, or the log would reach 2^32 - 2 entries"; return ZKGPU_ERR_ARG; }
+  return ZKGPU_OK; }); }
+int zkgpu_accts_rewind(zkgpu_accts *a, uint64_t size) { return guarded_accts(a, [&] {
+  if (!a->a.rewind(size)) { g_err = "account table: cannot rewind to " + std::to_string(size) + " entries, the table holds fewer"; return ZKGPU_ERR_ARG; }
+  return ZKGPU_OK; }); }
+int zkgpu_accts_read_log(zkgpu_accts *a, uint64_t first, uint64_t count, uint8_t *entries) { return guarded_accts(a, [&] {
+  if (!a->a.read_log(first, count, entries)) { g_err = "account table: the range leaves the log, or a null pointer"; return ZKGPU_ERR_ARG; }
+  return ZKGPU_OK; }); }
+int zkgpu_test_accts_slots(zkgpu_accts *a, uint32_t *slots, uint64_t *n_slots, uint64_t *seed, uint64_t *tombstones) { return guarded_accts(a, [&] {
+  if (!n_slots || !seed || !tombstones) return ZKGPU_ERR_ARG;
+  std::vector<uint32_t> t; uint64_t sd = 0, tb = 0; a->a.table(t, sd, tb);
+  if (slots) { if (*n_slots != t.size()) { g_err = "account table: the table has " + std::to_string(t.size()) + " slots"; return ZKGPU_ERR_ARG; } memcpy(slots, t.data(), 4 * t.size()); }
+  *n_slots = t.size(); *seed = sd; *tombstones = tb; return ZKGPU_OK; }); }
+int zkgpu_test_accts_chain_cap(zkgpu_accts *a, uint32_t cap) { return guarded_accts(a, [&] { a->a.set_chain_cap(cap); return ZKGPU_OK; }); }
+int zkgpu_test_accts_launches(uint64_t *launches, uint64_t *host_finishes) {
+  if (!launches || !host_finishes) return ZKGPU_ERR_ARG;
+  if (!gpu_available()) { g_err = "no HIP device visible; libzkgpu has no CPU fallback"; return ZKGPU_ERR_NO_DEVICE; }
+  AccountTable::launches(*launches, *host_finishes); return ZKGPU_OK; }
 }  // extern "C"

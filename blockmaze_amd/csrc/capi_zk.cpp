@@ -39,8 +39,10 @@
 #include "../../include/zk_spent_pk.h"
 #include "../../include/zk_tree_block.h"
 #include "../../include/zk_tree_chain.h"
+#include "../../include/zk_accounts.h"
 #include "../../include/zkgpu.h"
 #include "blockmaze_circuits.hpp"
+#include "capi_accounts.hpp"
 #include "groth16.hpp"
 
 using namespace zk;
@@ -1927,6 +1929,78 @@ int verifyBlockTree(zk_proof_cache *cache, const zk_block_record *recs, int n, z
     if (set && set_size_out) *set_size_out = (long long)set_size;
     if (tree_size_out) *tree_size_out = (long long)tree->t.size();
     return accepted;
+  }
+  catch (const std::exception &e) { return fail(e.what()); }
+  catch (...) { return fail("unknown error"); }
+}
+
+// ---- the account table at the drop-in level, and a block decided with it (DESIGN.md "Account table"; include/zk_accounts.h) -------------------------------------
+zk_accts *zkAcctsNew(void) { return zkgpu_accts_create(); }
+void zkAcctsFree(zk_accts *accts) { zkgpu_accts_destroy(accts); }
+long long zkAcctsSize(zk_accts *accts) { uint64_t n = 0; return zkgpu_accts_size(accts, &n) == ZKGPU_OK ? (long long)n : -1; }
+static int accts_rc(int rc, const char *who) { if (rc == ZKGPU_OK) return 0; fprintf(stderr, "libzkgpu: %s: %s\n", who, zkgpu_last_error()); return -1; }
+int zkAcctsSet(zk_accts *accts, const uint8_t (*addrs)[20], const uint8_t (*values)[32], int n) {
+  if (n < 0) { zkgpu_set_error("a negative count"); return accts_rc(ZKGPU_ERR_ARG, "zkAcctsSet"); }
+  return accts_rc(zkgpu_accts_set(accts, (const uint8_t *)addrs, (const uint8_t *)values, (size_t)n), "zkAcctsSet"); }
+int zkAcctsGet(zk_accts *accts, const uint8_t (*addrs)[20], int n, long long at_size, uint8_t (*out)[32]) {
+  if (n < 0) { zkgpu_set_error("a negative count"); return accts_rc(ZKGPU_ERR_ARG, "zkAcctsGet"); }
+  return accts_rc(zkgpu_accts_get(accts, (const uint8_t *)addrs, (size_t)n, (int64_t)at_size, (uint8_t *)out), "zkAcctsGet"); }
+int zkAcctsRewind(zk_accts *accts, long long size) {
+  if (size < 0) { zkgpu_set_error("a negative size"); return accts_rc(ZKGPU_ERR_ARG, "zkAcctsRewind"); }
+  return accts_rc(zkgpu_accts_rewind(accts, (uint64_t)size), "zkAcctsRewind"); }
+int zkAcctsFillRecords(zk_accts *accts, const uint8_t (*froms)[20], zk_block_record *recs, int n, int chained) {
+  if (n < 0) { zkgpu_set_error("a negative count"); return accts_rc(ZKGPU_ERR_ARG, "zkAcctsFillRecords"); }
+  return accts_rc(zkgpu_accts_fill(accts, (const uint8_t *)froms, recs, (size_t)n, chained), "zkAcctsFillRecords"); }
+// The table's mutex is held only inside fill and commit_chain, never together with the cache's, the set's or the tree's: verifyBlockTree runs between the two.
+int verifyBlockAccounts(zk_proof_cache *cache, zk_block_record *recs, const uint8_t (*froms)[20], int n, zk_accts *accts, zk_tree *tree, const long long *anchors,
+                        int n_anchors, zk_snset *set, int commit, unsigned char *ok, int32_t *anchor_of, long long *accts_size_out, long long *set_size_out,
+                        long long *tree_size_out) {
+  auto fail = [&](const std::string &why) {
+    zkgpu_set_error(why); fprintf(stderr, "libzkgpu: verifyBlockAccounts: %s\n", why.c_str());
+    for (int i = 0; i < n; i++) { if (ok) ok[i] = 0; if (anchor_of) anchor_of[i] = -1; }
+    return -1; };
+  try {
+    // 1. the arguments — verifyBlockTree's among them, which it looks at again — before anything is queued and before recs is written
+    if (n < 0 || (n && (!recs || !ok || !froms))) return fail("a negative count or a null pointer");
+    if (!accts) return fail("no account table");
+    if (n_anchors < 0 || (n_anchors && !anchors)) return fail("a negative number of anchors or a null pointer");
+    if (!gpu_available()) return fail("no HIP device visible; libzkgpu has no CPU fallback");
+    if (tree) {
+      const uint64_t size0 = tree->t.size();
+      for (int a = 0; a < n_anchors; a++) if (anchors[a] < 0 || (uint64_t)anchors[a] > size0) return fail("anchor " + std::to_string(a) + " is negative or above the tree's size");
+      if (commit) { uint64_t sends = 0; for (int i = 0; i < n; i++) sends += recs[i].kind == ZK_KIND_SEND; if (sends > (1ull << tree->t.depth()) - size0) return fail("the block's sends do not fit into the tree"); }
+    }
+    // 2. every record's old balance commitment from the table, chained through the block
+    if (zkgpu_accts_fill(accts, (const uint8_t *)froms, recs, (size_t)n, 1) != ZKGPU_OK) return fail(zkgpu_last_error());
+    // 3. verifyBlockTree's road on the statements as they now stand
+    uint64_t set_before = 0, tree_before = 0;
+    if (commit) { if (set) set_before = set->s.size(); if (tree) tree_before = tree->t.size(); }
+    long long set_size = -1, tree_size = -1;
+    if (verifyBlockTree(cache, recs, n, tree, anchors, n_anchors, set, commit, ok, anchor_of, &set_size, &tree_size) < 0) return -1;   // (it has written the failure's outputs)
+    // 4. the first rejected record ends the block: what follows it was verified under an assumption that does not hold
+    int f = 0; while (f < n && ok[f]) f++;
+    auto take_back = [&]() -> bool {                                                                // the shrink of "A stretch of the chain": set and tree to their sizes before the call
+      bool good = true;
+      if (set) { try { good = set->s.rewind(set_before) && good; } catch (const std::exception &e) { good = false; fprintf(stderr, "libzkgpu: verifyBlockAccounts: the spent set could not be rewound (%s)\n", e.what()); } }
+      if (tree) { try { good = tree->t.rewind(tree_before) && good; } catch (const std::exception &e) { good = false; fprintf(stderr, "libzkgpu: verifyBlockAccounts: the tree could not be rewound (%s)\n", e.what()); } }
+      return good; };
+    // a failure after verifyBlockTree has committed that the rewinds could not undo: the one -1 that may leave the set or the tree changed.  The three sizes as they
+    // now are go to the caller, who can rewind to the sizes it stored before the call.
+    auto fail_after = [&](const std::string &why) {
+      if (accts_size_out) *accts_size_out = (long long)accts->a.size();
+      if (set && set_size_out) *set_size_out = (long long)set->s.size();
+      if (tree_size_out) *tree_size_out = tree ? (long long)tree->t.size() : -1;
+      return fail(why + " (the sizes after the call are reported)"); };
+    if (f < n) {
+      for (int i = f + 1; i < n; i++) { ok[i] = 0; if (anchor_of) anchor_of[i] = -1; }
+      if (commit) { if (!take_back()) return fail_after("the set or the tree could not be rewound: another writer changed it during the call"); set_size = (long long)set_before; if (tree) tree_size = (long long)tree_before; }
+    } else if (commit && n) {
+      if (zkgpu_accts_commit_chain(accts, (const uint8_t *)froms, recs, (size_t)n) != ZKGPU_OK) { const std::string why = zkgpu_last_error(); return take_back() ? fail(why) : fail_after(why + "; the set or the tree could not be rewound either"); }
+    }
+    if (accts_size_out) *accts_size_out = (long long)accts->a.size();
+    if (set && set_size_out) *set_size_out = set_size;
+    if (tree_size_out) *tree_size_out = tree_size;
+    return f;
   }
   catch (const std::exception &e) { return fail(e.what()); }
   catch (...) { return fail("unknown error"); }

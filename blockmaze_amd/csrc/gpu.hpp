@@ -239,6 +239,31 @@ class SpentSet {
 // with code 2 where a key is in that set or k1 == k2.  No live record has a resident key: the first round rejected those.
 void snset_pairs_finish_host(const uint8_t *keys, const uint8_t *active, size_t n, uint8_t *status, uint8_t *code);
 
+// The account table resident in HBM (gpu_accounts.hip; DESIGN.md "Account table"): a map from a 20-byte address to a 32-byte value as an append-only log of (address,
+// value, prev) entries and the spent set's index over it, a slot holding the address's latest entry; state m = the first m log entries, and the value of an address
+// at state m is that of its latest entry below m, or 32 zero bytes.  One mutex per table (taken before the device mutex): every entry is atomic with respect to the
+// others.  false = a bad argument (a size above size(), a null pointer with a count, a log that would reach 2^32 - 2 entries): nothing is written and nothing
+// changes.  Records are zk_block_record (include/zk_records.h) as bytes, 720 each; a record whose kind is above 3 takes no part.  There is no host table.
+class AccountTable {
+ public:
+  explicit AccountTable(int log2_slots = 0 /* tests: a table of 2^4 slots or more; 0 = 2^10 */, const uint64_t *seed = nullptr /* tests; null = getrandom */);
+  ~AccountTable();
+  uint64_t size() const;
+  // unconditional and in order (addrs: n x 20 bytes, values: n x 32): every record becomes a log entry, a repeated address ends at its last record's value
+  bool set(const uint8_t *addrs, const uint8_t *values, size_t n, uint64_t *size_out /* or null */);
+  bool get(const uint8_t *addrs, size_t q, int64_t at_size /* -1 = current */, uint8_t *out /* q x 32 */);   // read-only, one launch
+  // the OLD slot of every record (and nothing else of it) becomes the sender's value: the table's current one, or — chained — the NEW slot of the closest earlier
+  // record of the call with the same sender.  The table is afterwards what it was, index included.
+  bool fill(const uint8_t *addrs, uint8_t *recs, size_t n, bool chained);
+  bool commit_chain(const uint8_t *addrs, const uint8_t *recs, size_t n, uint64_t *size_out /* or null */);   // set() with the values read from the records' NEW slots
+  bool rewind(uint64_t size);                                                 // the table becomes state `size`
+  bool read_log(uint64_t first, uint64_t count, uint8_t *out);                // entries first .. first + count - 1: 56 bytes each — address 20, value 32, prev as a little-endian word
+  void table(std::vector<uint32_t> &slots, uint64_t &seed, uint64_t &tombstones);   // tests: the index as it lies in device memory
+  void set_chain_cap(uint32_t cap);                                           // tests: the list walk's cap of this table; 0 = the default
+  static void launches(uint64_t &launches, uint64_t &host_finishes);          // kernels launched and predecessor searches finished on the host, by all tables of the process (tests)
+  struct Impl; std::unique_ptr<Impl> impl;
+};
+
 // The proof cache (gpu_proof_cache.hip; DESIGN.md "Proof cache").  The key of a record is the first 20 bytes of SHA-256(salt[32] || vktag[32] || record[720]).
 // record_digests_dev: the keys of n records on the device (k_record_digest).  mid: the SHA-256 states after the block salt || vktag, eight words for each of the kinds
 // 0..3; kinds: bit k set = kind k has a key; a record of any other kind gets 20 zero bytes.  The caller holds the device mutex; runs on the main stream and returns

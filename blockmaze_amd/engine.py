@@ -479,6 +479,56 @@ def record_sn(rec):
     """the serial number a record (RECORD_DTYPE) spends, the 32 bytes of its common.Hash: snold = args[3] for deposit, args[1] for mint, send and redeem; the set's key is [12:]"""
     return bytes(rec["args"][3 if int(rec["kind"]) == KIND["deposit"] else 1])
 
+# ---- the account table resident in HBM (include/zkgpu.h "the account table"; the drop-in level is include/zk_accounts.h) ----
+ACCT_OLD_ARG = {0: 0, 1: 0, 2: 2, 3: 0}   # kind -> the args entry that holds the sender's balance commitment before the record
+ACCT_NEW_ARG = {0: 2, 1: 3, 2: 4, 3: 2}   # ... and after it
+def _vals32(values):
+    buf = values.tobytes() if isinstance(values, np.ndarray) else bytes(values) if isinstance(values, (bytes, bytearray)) else b"".join(bytes(v) for v in values)
+    assert len(buf) % 32 == 0; return buf, len(buf) // 32
+class AccountTable:
+    """a map from 20-byte addresses to 32-byte values on the device: an append-only log of (address, value, prev) entries and an index over it; state m = the first
+    m entries, the value of an address at state m = that of its latest entry below m, or 32 zero bytes"""
+    def __init__(self, log2_slots=None, seed=0):
+        """log2_slots: the test entry (a table of 2^log2_slots slots and the given seed); otherwise 2^10 slots and a seed from getrandom"""
+        L = lib(); L.zkgpu_accts_create.restype = ctypes.c_void_p; L.zkgpu_test_accts_create.restype = ctypes.c_void_p
+        self.h = L.zkgpu_accts_create() if log2_slots is None else L.zkgpu_test_accts_create(int(log2_slots), ctypes.c_uint64(seed))
+        if not self.h: raise ZkGpuError(lib().zkgpu_last_error().decode())
+    def size(self):
+        n = ctypes.c_uint64(0); _check(lib().zkgpu_accts_size(ctypes.c_void_p(self.h), ctypes.byref(n))); return int(n.value)
+    def set(self, addrs, values):
+        ab, n = _keys20(addrs); vb, nv = _vals32(values); assert n == nv; _check(lib().zkgpu_accts_set(ctypes.c_void_p(self.h), ab, vb, ctypes.c_size_t(n)))
+    def get(self, addrs, at_size=-1):
+        """-> [32-byte value of each address at state at_size (-1: now)]"""
+        ab, n = _keys20(addrs); out = ctypes.create_string_buffer(max(1, 32 * n))
+        _check(lib().zkgpu_accts_get(ctypes.c_void_p(self.h), ab, ctypes.c_size_t(n), ctypes.c_int64(at_size), out)); return [out.raw[32 * i:32 * i + 32] for i in range(n)]
+    def fill(self, addrs, recs, chained):
+        """-> a copy of the records (RECORD_DTYPE) with their old slots filled"""
+        ab, n = _keys20(addrs); recs = np.array(recs, dtype=RECORD_DTYPE, copy=True); assert recs.shape == (n,)
+        _check(lib().zkgpu_accts_fill(ctypes.c_void_p(self.h), ab, recs.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(n), int(bool(chained)))); return recs
+    def commit_chain(self, addrs, recs):
+        ab, n = _keys20(addrs); recs, ptr, nr = _recs(recs); assert n == nr; _check(lib().zkgpu_accts_commit_chain(ctypes.c_void_p(self.h), ab, ptr, ctypes.c_size_t(n)))
+    def rewind(self, size): _check(lib().zkgpu_accts_rewind(ctypes.c_void_p(self.h), ctypes.c_uint64(size)))
+    def read_log(self, first=0, count=None):
+        """-> [(20-byte address, 32-byte value, prev)] of log entries first .. first + count - 1 (count None: to the end)"""
+        count = self.size() - first if count is None else count; out = ctypes.create_string_buffer(max(1, 56 * count))
+        _check(lib().zkgpu_accts_read_log(ctypes.c_void_p(self.h), ctypes.c_uint64(first), ctypes.c_uint64(count), out))
+        return [(out.raw[56 * i:56 * i + 20], out.raw[56 * i + 20:56 * i + 52], int.from_bytes(out.raw[56 * i + 52:56 * i + 56], "little")) for i in range(count)]
+    def slots(self):
+        """test entry -> (the index as a uint32 array, the seed, the host's tombstone count)"""
+        n = ctypes.c_uint64(0); seed = ctypes.c_uint64(0); tombs = ctypes.c_uint64(0); h = ctypes.c_void_p(self.h)
+        _check(lib().zkgpu_test_accts_slots(h, None, ctypes.byref(n), ctypes.byref(seed), ctypes.byref(tombs))); t = np.zeros(int(n.value), dtype=np.uint32)
+        _check(lib().zkgpu_test_accts_slots(h, t.ctypes.data_as(ctypes.c_void_p), ctypes.byref(n), ctypes.byref(seed), ctypes.byref(tombs))); return t, int(seed.value), int(tombs.value)
+    def chain_cap(self, cap): _check(lib().zkgpu_test_accts_chain_cap(ctypes.c_void_p(self.h), ctypes.c_uint32(cap)))   # test entry: 0 = the default
+    def close(self):
+        if self.h: lib().zkgpu_accts_destroy(ctypes.c_void_p(self.h)); self.h = None
+    def __del__(self):
+        try: self.close()
+        except Exception: pass
+def accts_launches():
+    """(kernels launched by all account tables of this process so far, predecessor searches the host finished)"""
+    k = ctypes.c_uint64(0); h = ctypes.c_uint64(0); _check(lib().zkgpu_test_accts_launches(ctypes.byref(k), ctypes.byref(h))); return int(k.value), int(h.value)
+def _accts_handle(a): return None if a is None else ctypes.c_void_p(a.h if isinstance(a, AccountTable) else a)
+
 # ---- the proof cache (include/zkgpu.h "the proof cache"; the drop-in level is include/zk_proof_cache.h) ----
 class ProofCache:
     """the records whose proof this process has accepted, by keyed digest, in two generations on the device.  salt: the test entry (32 given bytes instead of getrandom)"""
@@ -704,5 +754,30 @@ class Zk:
         rc = self.L.verifyChainTree(_cache_handle(cache), ptr, n, bf.ctypes.data_as(ctypes.c_void_p) if nb >= 0 else None, nb, ctypes.c_void_p(tree) if tree else None, pa.ctypes.data_as(ctypes.c_void_p) if npa else None, npa,
                                     int(window), ctypes.c_void_p(s) if s else None, ok, of, ss.ctypes.data_as(ctypes.c_void_p), ts.ctypes.data_as(ctypes.c_void_p))
         return (rc, [bool(ok[i]) for i in range(n)], [int(of[i]) for i in range(n)], ([int(x) for x in ss[:nb]] if rc >= 0 and s else None), ([int(x) for x in ts[:nb]] if rc >= 0 else None))
+    # include/zk_accounts.h: the resident account table at the drop-in level, and a block decided with it.  a: a handle of AcctsNew or an AccountTable
+    def AcctsNew(self): self.L.zkAcctsNew.restype = ctypes.c_void_p; return self.L.zkAcctsNew()   # None on failure
+    def AcctsFree(self, a): self.L.zkAcctsFree(_accts_handle(a))
+    def AcctsSize(self, a): self.L.zkAcctsSize.restype = ctypes.c_longlong; return int(self.L.zkAcctsSize(_accts_handle(a)))
+    def AcctsSet(self, a, addrs, values):
+        ab, n = _keys20(addrs); vb, nv = _vals32(values); assert n == nv; return int(self.L.zkAcctsSet(_accts_handle(a), ab, vb, n))
+    def AcctsGet(self, a, addrs, at_size=-1):
+        """-> [32-byte value], None on failure"""
+        ab, n = _keys20(addrs); out = ctypes.create_string_buffer(max(1, 32 * n)); rc = self.L.zkAcctsGet(_accts_handle(a), ab, n, ctypes.c_longlong(at_size), out)
+        return [out.raw[32 * i:32 * i + 32] for i in range(n)] if rc == 0 else None
+    def AcctsRewind(self, a, size): return int(self.L.zkAcctsRewind(_accts_handle(a), ctypes.c_longlong(size)))
+    def AcctsFillRecords(self, a, froms, items, chained):
+        """-> (0 / -1, a copy of the records with their old slots filled)"""
+        recs = items if isinstance(items, np.ndarray) else records_from_items(items); recs = np.array(recs, dtype=RECORD_DTYPE, copy=True); n = int(recs.shape[0]); fb, nf = _keys20(froms); assert nf == n
+        rc = int(self.L.zkAcctsFillRecords(_accts_handle(a), fb if n else None, recs.ctypes.data_as(ctypes.c_void_p), n, int(bool(chained)))); return rc, recs
+    def VerifyBlockAccounts(self, cache, items, froms, a, tree, anchors, s, commit):
+        """-> (leading accepted records or -1, [bool], [anchor_of], the records as they were verified, table size after or None, set size after or None, tree size after or None)"""
+        recs = items if isinstance(items, np.ndarray) else records_from_items(items); recs = np.array(recs, dtype=RECORD_DTYPE, copy=True); n = int(recs.shape[0]); fb, nf = _keys20(froms); assert nf == n
+        an = np.ascontiguousarray(anchors if anchors is not None else [], dtype=np.int64).reshape(-1); na = int(an.size)
+        ok = (ctypes.c_ubyte * max(1, n))(); of = (ctypes.c_int32 * max(1, n))(*([-7] * max(1, n))); asize = ctypes.c_longlong(-7); size = ctypes.c_longlong(-7); tsize = ctypes.c_longlong(-7)
+        self.L.verifyBlockAccounts.restype = ctypes.c_int
+        rc = self.L.verifyBlockAccounts(_cache_handle(cache), recs.ctypes.data_as(ctypes.c_void_p), fb if n else None, n, _accts_handle(a), ctypes.c_void_p(tree) if tree else None,
+                                        an.ctypes.data_as(ctypes.c_void_p) if na else None, na, ctypes.c_void_p(s) if s else None, int(bool(commit)), ok, of, ctypes.byref(asize), ctypes.byref(size), ctypes.byref(tsize))
+        return (rc, [bool(ok[i]) for i in range(n)], [int(of[i]) for i in range(n)], recs, (None if asize.value == -7 else int(asize.value)), (None if size.value == -7 else int(size.value)),
+                (None if tsize.value < 0 else int(tsize.value)))
     def VerifyDepositProofDepth(self, depth, proof, RT, pk, cmtb_old, sn_old, cmtb, sns):
         return bool(self.L.verifyDepositproofDepth(int(depth), proof.encode(), self.hx(RT), self.hx(pk), self.hx(cmtb_old), self.hx(sn_old), self.hx(cmtb), self.hx(sns)))

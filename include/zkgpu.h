@@ -334,6 +334,43 @@ zkgpu_proof_cache *zkgpu_test_proof_cache_create(uint64_t capacity, const uint8_
 int zkgpu_test_record_digests(const uint8_t salt[32], const uint8_t tags[4][32], const zk_block_record *recs, size_t n, int device, uint8_t *out20);
 int zkgpu_test_proof_cache_launches(uint64_t *launches);
 
+/* ---- the account table resident in HBM (DESIGN.md "Account table"; the drop-in level is zk_accounts.h) -----------------------------------------------------
+ * A map from a 20-byte address to a 32-byte value: an append-only log of entries of 14 words — the address (5), the value (8) and prev (1: log index + 1 of the
+ * address's previous entry, or 0) — and an index over it; state m is the first m entries, 0 <= m <= size, and the value of an address at state m is the value of
+ * its latest entry below m, or 32 zero bytes.  The index is the spent set's: 32-bit slots, a power of two of them (2^10 at least), linear probing from the home slot
+ * of the mix stated above; a slot holds 0, 0xFFFFFFFF (a tombstone, left by a rewind) or log index + 1 of the address's LATEST entry.  Entries + tombstones + the
+ * incoming batch stay at or below half of the slots: otherwise the table is first rebuilt from the log at the smallest sufficient size.
+ * Every call is one upload and one download whatever n is, with two exceptions: a batch in which one address has more records than the chain cap adds the host's
+ * search, one upload and one download; and the first get, rewind or unchained fill after a call that failed midway rebuilds the index first and reads the rebuild's
+ * error word back, one more download.  ZKGPU_ERR_ARG, with nothing written and nothing changed, for a size above the current size, a null
+ * pointer where a count is not 0, or a log that would reach 2^32 - 2 entries.  ZKGPU_ERR_NO_DEVICE without a device: there is no host table.  Entries of one table
+ * are atomic with respect to each other and may be called from any thread. */
+typedef struct zkgpu_accts zkgpu_accts;
+zkgpu_accts *zkgpu_accts_create(void);                                       /* NULL + zkgpu_last_error() on failure */
+void zkgpu_accts_destroy(zkgpu_accts *a);
+int zkgpu_accts_size(zkgpu_accts *a, uint64_t *n);
+/* addrs[i] (n x 20 bytes) gets values[i] (n x 32), unconditionally and in record order: every record becomes a log entry, and an address that repeats ends at its
+ * last record's value.  Three launches. */
+int zkgpu_accts_set(zkgpu_accts *a, const uint8_t *addrs, const uint8_t *values, size_t n);
+/* out[i] (n x 32) = the value of addrs[i] at state at_size; at_size = -1: the current state.  Read-only, one launch, one lane a query. */
+int zkgpu_accts_get(zkgpu_accts *a, const uint8_t *addrs, size_t n, int64_t at_size, uint8_t *out);
+/* The OLD slot of each record with kind <= 3 — args[0] for mint, send and redeem, args[2] for deposit — is overwritten with the value of addrs[i], and nothing else
+ * of the record's 720 bytes.  chained = 0: the table's current value (one launch).  chained != 0: the NEW slot — args[2] mint / redeem, args[3] send, args[4]
+ * deposit — of the closest earlier record of the call with the same address and kind <= 3, else the table's value (three launches).  The table does not change,
+ * index included. */
+int zkgpu_accts_fill(zkgpu_accts *a, const uint8_t *addrs, zk_block_record *recs, size_t n, int chained);
+/* zkgpu_accts_set with the values read from the NEW slots of the records with kind <= 3; the others add nothing */
+int zkgpu_accts_commit_chain(zkgpu_accts *a, const uint8_t *addrs, const zk_block_record *recs, size_t n);
+int zkgpu_accts_rewind(zkgpu_accts *a, uint64_t size);                       /* the table becomes state `size`; size 0 empties it */
+int zkgpu_accts_read_log(zkgpu_accts *a, uint64_t first, uint64_t count, uint8_t *entries /* count x 56: address, value, prev as a little-endian word */);
+/* test entries: a table of 2^log2_slots slots (4 .. 31; it still grows) with a given seed; the index as it lies in device memory (as zkgpu_test_snset_slots); the
+ * number of list steps of this table after which a batch's predecessor search goes to the host (0 = the default, 256); the process-wide numbers of kernels
+ * launched by all tables and of searches the host finished */
+zkgpu_accts *zkgpu_test_accts_create(int log2_slots, uint64_t seed);
+int zkgpu_test_accts_slots(zkgpu_accts *a, uint32_t *slots, uint64_t *n_slots, uint64_t *seed, uint64_t *tombstones);
+int zkgpu_test_accts_chain_cap(zkgpu_accts *a, uint32_t cap);
+int zkgpu_test_accts_launches(uint64_t *launches, uint64_t *host_finishes);
+
 #ifdef __cplusplus
 }
 #endif
