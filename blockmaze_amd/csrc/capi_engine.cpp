@@ -113,6 +113,22 @@ int zkgpu_msm_run(zkgpu_msm *h, uint8_t *out) { return guarded([&] { if (!h) ret
   if (h->group == 1) { h->g1->run(h->scalars.get(), nullptr); g1_out(h->g1->result(), out); } else { h->g2->run(h->scalars.get(), nullptr);
       g2_out(h->g2->result(), out); } return ZKGPU_OK; }); }
 void zkgpu_msm_destroy(zkgpu_msm *h) { guarded([&] { delete h; return ZKGPU_OK; }); }
+// test entry points of the uniform-scalar (H query) path: which path the object takes, and what a one-pass run left on the device (gpu.hpp: MsmG1::test_path)
+int zkgpu_test_msm_path(zkgpu_msm *h, uint32_t out[24]) { return guarded([&] { if (!h || h->group != 1 || !out) { g_err = "a G1 MSM object";
+    return ZKGPU_ERR_ARG; }
+  static_assert(MsmG1::TEST_PATH_WORDS == 24, "zkgpu.h says 24 words"); h->g1->test_path(out); return ZKGPU_OK; }); }
+int zkgpu_test_msm_set_crowded(zkgpu_msm *h, int on) { return guarded([&] { if (!h || h->group != 1) { g_err = "a G1 MSM object"; return ZKGPU_ERR_ARG; }
+  h->g1->set_crowded(on != 0); return ZKGPU_OK; }); }
+int zkgpu_test_msm_run_product(zkgpu_msm *h, const uint8_t *a, const uint8_t *b, const uint8_t *z, int z_is_table, uint8_t out[64]) {
+  return guarded([&] { if (!h || h->group != 1 || !h->n || !a || !b || !z || !out) { g_err = "a non-empty G1 MSM object and three operands"; return ZKGPU_ERR_ARG; }
+    // (the operands stay alive until result() has synchronised: a fallback reads them again)
+    const size_t n = h->n, nz = z_is_table ? n : 1; DevBuf<Fe32> da(n), db(n), dz(nz);
+    da.upload((const Fe32 *)a, n); db.upload((const Fe32 *)b, n); dz.upload((const Fe32 *)z, nz);
+    fr_to_mont_dev(da.get(), n); fr_to_mont_dev(db.get(), n); fr_to_mont_dev(dz.get(), nz); gpu_sync();
+    h->g1->run_product(da.get(), db.get(), dz.get(), z_is_table != 0); g1_out(h->g1->result(), out); return ZKGPU_OK; }); }
+int zkgpu_test_msm_h_state(zkgpu_msm *h, int what, uint32_t *out, size_t cap_words, size_t *words) {
+  return guarded([&] { if (!h || h->group != 1 || !out || !words) { g_err = "a G1 MSM object"; return ZKGPU_ERR_ARG; }
+    *words = h->g1->test_h_state(what, out, cap_words); return ZKGPU_OK; }); }
 static int msm_oneshot(int group, const uint8_t *points, const uint8_t *scalars, size_t n, int c, int fo, uint8_t *out) {
   zkgpu_msm *h = zkgpu_msm_create(group, points, n, c, fo);
   if (!h) return ZKGPU_ERR_RUNTIME;

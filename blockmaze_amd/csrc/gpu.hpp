@@ -102,6 +102,14 @@ class MsmG1 {
   void set_label(const char *l);
   void set_stream(int aux /* -1 main, 0..3 auxiliary */);
   void split_ones_path();
+  // test entry points (zkgpu_test_msm_*): what the constructor decided — out[0..23] = one_pass_sort, c, W, NB | HsortShape groups, low_bits, idx_bits, region |
+  // h_run, h_maxp, htail29, lane exponent of the last combine | the run in effect (crowded or not), any point at infinity, WB, result slots | HtailShape top,
+  // lo_bits, hi_bits, row_chunks | workgroup size of k_hmarg29, its workgroups, marginal records, the flag word of the last one-pass run (MsmCounters::pad[0]: bit 0 an
+  // overflow or a degenerate bucket sum, bit 1 a degenerate sum of the tail with its result slots from bit 8 on) — and what the last synchronised one-pass run left on the
+  // device: what = 0 counts, 1 offsets (a word a bucket), 2 entries of each group, 3 the sorted entries (groups x region), 4 the bucket sums (Point29Rec, 48 words
+  // a bucket).  Returns the number of words written; throws if `cap_words` is too small or the object has no such state.
+  static constexpr int TEST_PATH_WORDS = 24;
+  void test_path(uint32_t out[TEST_PATH_WORDS]) const; size_t test_h_state(int what, uint32_t *out, size_t cap_words);
   struct Impl; std::unique_ptr<Impl> impl;
 };
 class MsmG2 {

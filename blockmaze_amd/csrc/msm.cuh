@@ -151,6 +151,34 @@ __global__ void __launch_bounds__(256) k_msm_scatter(const Fr *__restrict__ scal
 //                  31.6 -> 17.3 us, +0.9 % proofs/s on one box, tools/ab_lib_value.sh.)  Emits counts[] / offsets[] and the number of entries of the group.  The entries keep their low bucket bits: k_hacc_runs29 finds the bucket boundaries by them.
 // Uniform scalars fill every group to within a few per cent of n*W/G, so a region holds 1.25x that; a region that would overflow raises a flag and the host
 // repeats the MSM on the two-pass path (any input stays correct).
+// The last window of a scalar holds only 254 - c (W - 1) of its bits — 7, 2, 14, 14, 16, 2, 7 for c = 13 .. 19 — so the n digits of that window land in a handful
+// of the lowest buckets (97 of them at c = 13 and 19, three at 14 and 18) and overflow their group's region and their pieces, sized for n W / NB entries a bucket:
+// every H query of a realistic size was repeated on the general path at those windows.  G1 has prime order r, so k P = (k + m r) P: scalar i is sorted as
+// k + m_i r with m_i one of `spread` = 2^(c W - 256) multiples picked by a hash of i.  The sum stays below 2^(c W - 2): W digits still, none carried out of the
+// top window, and the top digit spreads over 0.19 NB buckets, a sixth more load there, as at c = 16 by itself.  spread = 1 (c = 15, 16, 17; the compiled-in digit
+// walks) leaves the scalar as it is.  The fallback on the general path sorts the scalars themselves.
+__host__ __device__ inline uint32_t hsort_spread(int c) { const int W = 254 / c + 1, tb = 254 - c * (W - 1); return tb < c - 2 && c * W > 256 ? 1u << (c * W - 256) : 1u; }
+__host__ __device__ inline uint32_t hsort_multiple(uint32_t i, uint32_t spread) { return spread > 1 ? ((i * 2654435761u) >> 16) % spread : 0u; }
+__device__ __forceinline__ void signed_digits9(const uint32_t k[9], int c, int W, int *dig) {   // signed_digits on nine words
+  uint32_t carry = 0; const uint32_t half = 1u << (c - 1), full = 1u << c, mask = full - 1;
+  for (int w = 0; w < W; w++) {
+    int bit = w * c, word = bit >> 5, sh = bit & 31;
+    uint64_t v = word < 9 ? k[word] : 0; if (word + 1 < 9) v |= (uint64_t)k[word + 1] << 32;
+    uint32_t d = ((uint32_t)(v >> sh) & mask) + carry;
+    if (d > half) { dig[w] = (int)d - (int)full; carry = 1; } else { dig[w] = (int)d; carry = 0; }
+  }
+}
+// fn(w, digit) for the H sort: the compiled-in walk as it is; the runtime one on k + m_i r
+template <int C, class Fn> __device__ __forceinline__ void hsort_walk_digits(const uint32_t (&k)[8], uint32_t i, uint32_t spread, int c, int W, Fn &&fn) {
+  if constexpr (C > 0) { msm_walk_digits<C>(k, c, W, fn); }
+  else {
+    const uint32_t m = hsort_multiple(i, spread); uint32_t k9[9]; uint64_t carry = 0;
+#pragma unroll
+    for (int j = 0; j < 8; j++) { const uint64_t t = (uint64_t)k[j] + (uint64_t)m * FrParams::MOD[j] + carry; k9[j] = (uint32_t)t; carry = t >> 32; }
+    k9[8] = (uint32_t)carry;
+    int dig[MSM_MAX_WINDOWS]; signed_digits9(k9, c, W, dig); for (int w = 0; w < W; w++) fn(w, dig[w]);
+  }
+}
 constexpr uint32_t HSORT_GROUPS = 1024 /* at most; the shape says how many are used */, HSORT_BIN_THREADS = 256, HSORT_PER_THREAD = 2,
     HSORT_TILE = HSORT_BIN_THREADS * HSORT_PER_THREAD, HSORT_GROUP_THREADS = 1024, HSORT_MAX_PER_THREAD = 24, HSORT_SLICES = 8,
     HSORT_STAGE_W = 20 /* staged entries per scalar: at most 254 / c + 1 digits, c >= 13 */;
@@ -159,7 +187,7 @@ struct HsortShape { uint32_t groups, low_bits, idx_bits, region; };
 template <int C>
 __global__ void __launch_bounds__(HSORT_BIN_THREADS) k_hsort_bin(const Fr *__restrict__ scalars, const Fr *__restrict__ mul_b, const Fr *__restrict__ mul_z,
     int z_is_table, const uint8_t *__restrict__ point_is_inf,
-                                                                 uint32_t n, int c, int W, uint32_t point_stride, HsortShape sh,
+                                                                 uint32_t n, int c, int W, uint32_t point_stride, HsortShape sh, uint32_t spread,
                                                                      uint32_t *__restrict__ group_fill, uint32_t *__restrict__ mid, MsmCounters *cnt,
                                                                      MsmCounters *cnt_next) {
   zk_take_prio(sh.low_bits);
@@ -179,7 +207,7 @@ __global__ void __launch_bounds__(HSORT_BIN_THREADS) k_hsort_bin(const Fr *__res
     if (live[q]) { Fr v = scalars[i]; if (mul_b) v = v * mul_b[i] * mul_z[z_is_table ? i : 0]; k[q] = v.from_mont(); live[q] = !k[q].is_zero(); } }
   const uint32_t low_mask = (1u << sh.low_bits) - 1;
 #pragma unroll
-  for (int q = 0; q < (int)HSORT_PER_THREAD; q++) if (live[q]) msm_walk_digits<C>(k[q].l, c, W, [&](int, int d) {
+  for (int q = 0; q < (int)HSORT_PER_THREAD; q++) if (live[q]) hsort_walk_digits<C>(k[q].l, blockIdx.x * HSORT_TILE + q * HSORT_BIN_THREADS + threadIdx.x, spread, c, W, [&](int, int d) {
       if (d) atomicAdd(&lcnt[((uint32_t)(d < 0 ? -d : d) - 1) >> sh.low_bits], 1u); });
   __syncthreads();
   // exclusive scan of the group counts (where each group's run starts in the staging tile) and the reservation of the runs in the groups' regions
@@ -206,7 +234,7 @@ __global__ void __launch_bounds__(HSORT_BIN_THREADS) k_hsort_bin(const Fr *__res
   __syncthreads();
 #pragma unroll
   for (int q = 0; q < (int)HSORT_PER_THREAD; q++) if (live[q]) { const uint32_t i = blockIdx.x * HSORT_TILE + q * HSORT_BIN_THREADS + threadIdx.x;
-    msm_walk_digits<C>(k[q].l, c, W, [&](int w, int d) { if (!d) return; const uint32_t key = (uint32_t)(d < 0 ? -d : d) - 1, g = key >> sh.low_bits,
+    hsort_walk_digits<C>(k[q].l, i, spread, c, W, [&](int w, int d) { if (!d) return; const uint32_t key = (uint32_t)(d < 0 ? -d : d) - 1, g = key >> sh.low_bits,
         p = atomicAdd(&lcnt[g], 1u);
       if (p < HSORT_TILE * HSORT_STAGE_W) { stage[p] = ((key & low_mask) << (sh.idx_bits + 1)) | ((d < 0 ? 1u : 0u) << sh.idx_bits) | (i +
           (uint32_t)w * point_stride); stage_g[p] = (uint16_t)g; } }); }

@@ -47,6 +47,7 @@ struct MsmImpl {
   // fewer general additions in the combine (12.6 -> 4.2 pieces a bucket at 40: -6 % of a proof's instructions; six provers in flight 1,730 -> 1,875 proofs/s,
   // prove_batch(64) 1,680 -> 1,860; 24 / 32 / 48: 1,843 / 1,858 / 1,835; profiles/r05_hacc_sweeps.txt).  One proof at a time keeps the short runs: its latency is the accumulation's last partial round.
   uint32_t h_run_crowded = 40; bool crowded = false;
+  uint32_t last_ll = 0, last_flag = 0;   // lane exponent of the last combine, flag word of the last one-pass run (what a test reads back: MsmG1::test_path)
   // witness MSMs in three launches (k_wsort / k_wacc / k_wtail); needs the fixed-base tables and at most 128 buckets
   bool wfused = false, ws_leader = true, overflow_noted = false; std::shared_ptr<WsortBuffers> ws;
   const Fe32 *last_scalars = nullptr; const uint32_t *last_index = nullptr;
@@ -328,6 +329,7 @@ struct MsmImpl {
             for (uint32_t b = 0; b < NB; b++) fwrite(en.data() + (size_t)b * ws->cap, 4, std::min(std::max(fl[b], fl[NB + b]), ws->cap), f);
             fwrite(p1.data(), 1, p1.size(), f); fwrite(p2.data(), 1, p2.size(), f); fclose(f); fprintf(stderr, "libzkgpu: %s: state written to %s\n", label.c_str(), path.c_str()); } } }
       wfused = false; run_impl(last_scalars, last_index); HIP_CHECK(hipStreamSynchronize(stream())); wfused = true; }
+    if (hsort) last_flag = host_counters()->pad[0];
     if (hsort && host_counters()->pad[0]) { const Fe32 *sc = last_scalars; hsort = false; note_general_path_repeat();
       // hist() held the bucket counts of the group sort; the two-pass path wants it cleared
       HIP_CHECK(hipMemsetAsync(zeroed.get(), 0, 2 * (size_t)WB * NB * sizeof(uint32_t), stream()));
@@ -433,7 +435,7 @@ struct MsmImpl {
       if constexpr (sizeof(F) == 32) {
       { Stage st((label + ".sort").c_str(), s);
         HsortShape hs_prio = hs; hs_prio.low_bits |= zk_prio_bits(ZKP_HSORT);
-#define ZK_CALL(CC) hipLaunchKernelGGL(k_hsort_bin<CC>, dim3(cdiv(n, HSORT_TILE)), dim3(HSORT_BIN_THREADS), 0, s, (const Fr *)scalars, (const Fr *)prod_b, (const Fr *)prod_z, (int)prod_z_table, infp, (uint32_t)n, c, W, point_stride, hs_prio, group_fill.get(), mid.get(), cnt, counters_next())
+#define ZK_CALL(CC) hipLaunchKernelGGL(k_hsort_bin<CC>, dim3(cdiv(n, HSORT_TILE)), dim3(HSORT_BIN_THREADS), 0, s, (const Fr *)scalars, (const Fr *)prod_b, (const Fr *)prod_z, (int)prod_z_table, infp, (uint32_t)n, c, W, point_stride, hs_prio, (CC) ? 1u : hsort_spread(c), group_fill.get(), mid.get(), cnt, counters_next())
         ZK_MSM_DISPATCH_C(c, ZK_CALL);
 #undef ZK_CALL
         static std::atomic<uint64_t> lds_done{0}; zk_raise_dynamic_lds(reinterpret_cast<const void *>(&k_hsort_group), 128 * 1024, lds_done);
@@ -456,6 +458,7 @@ struct MsmImpl {
         const uint32_t h_run = crowded ? std::max(this->h_run, h_run_crowded) : this->h_run;
         const size_t pieces = n * (size_t)W / NB / h_run;
         const uint32_t ll = pieces > 40 ? 3 : pieces > 18 ? 2 : 1;   // (send, runs of 14: 9 pieces; two and four lanes measure the same, eight lose 30 us)
+        last_ll = ll;
         hipLaunchKernelGGL(k_hacc_combine29, dim3(cdiv(nbk << ll, 256)), dim3(256), 0, s, (const Piece29 *)partials.get(), offsets.get(), hist(), hs, h_run,
             h_maxp, (uint32_t)nbk, zk_with_prio(ll, ZKP_HTAIL), (XYZZ<Fq> *)bucket_array(), htail29 ? (Point29Rec *)hb29.get() : nullptr, cnt);
       }

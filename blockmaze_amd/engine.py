@@ -94,6 +94,26 @@ class ResidentMsm:
         scalars = np.ascontiguousarray(scalars, dtype=np.uint64); _check(lib().zkgpu_msm_set_scalars(ctypes.c_void_p(self.h), _bytes(scalars), ctypes.c_size_t(scalars.size // 4)))
     def run(self):
         out = np.zeros(8 if self.group == 1 else 16, dtype=np.uint64); _check(lib().zkgpu_msm_run(ctypes.c_void_p(self.h), _bytes(out))); return out
+    # test entry points of the uniform-scalar (H query) path, G1 only (include/zkgpu.h: zkgpu_test_msm_*)
+    PATH_FIELDS = ("one_pass", "c", "W", "NB", "groups", "low_bits", "idx_bits", "region", "h_run", "h_maxp", "htail29", "ll", "run_in_effect", "any_inf", "WB", "RS",
+                   "top", "lo_bits", "hi_bits", "row_chunks", "marg_block", "marg_blocks", "marg_count", "flag")
+    H_STATE = {"counts": 0, "offsets": 1, "group_n": 2, "entries": 3, "hb29": 4}
+    def path(self):
+        """what the object decided when it was created (and the lane exponent of its last combine), as a namespace of ints; one_pass is a bool"""
+        import types
+        out = np.zeros(len(self.PATH_FIELDS), dtype=np.uint32); _check(lib().zkgpu_test_msm_path(ctypes.c_void_p(self.h), _u32(out)))
+        d = {k: int(v) for k, v in zip(self.PATH_FIELDS, out)}; d["one_pass"] = bool(d["one_pass"]); d["htail29"] = bool(d["htail29"]); return types.SimpleNamespace(**d)
+    def set_crowded(self, on): _check(lib().zkgpu_test_msm_set_crowded(ctypes.c_void_p(self.h), int(bool(on))))
+    def run_product(self, a, b, z):
+        """sum_i (a_i b_i z_i) P_i, the product formed inside the sort kernel; z: one element (4 words) or a table of n"""
+        a, b, z = (np.ascontiguousarray(x, dtype=np.uint64).reshape(-1, 4) for x in (a, b, z)); assert a.shape[0] == self.n == b.shape[0] and z.shape[0] in (1, self.n)
+        out = np.zeros(8, dtype=np.uint64)
+        _check(lib().zkgpu_test_msm_run_product(ctypes.c_void_p(self.h), _bytes(a), _bytes(b), _bytes(z), int(z.shape[0] == self.n and self.n > 1), _bytes(out))); return out
+    def h_state(self, what):
+        """device state of the last one-pass run (only meaningful when it did not fall back): uint32 words, see H_STATE"""
+        p = self.path(); cap = {"counts": p.NB, "offsets": p.NB, "group_n": p.groups, "entries": p.groups * p.region, "hb29": p.NB * 48}[what]
+        out = np.zeros(max(cap, 1), dtype=np.uint32); words = ctypes.c_size_t(0)
+        _check(lib().zkgpu_test_msm_h_state(ctypes.c_void_p(self.h), self.H_STATE[what], _u32(out), ctypes.c_size_t(out.size), ctypes.byref(words))); return out[:words.value]
     def close(self):
         if self.h: lib().zkgpu_msm_destroy(ctypes.c_void_p(self.h)); self.h = None
     def __del__(self):

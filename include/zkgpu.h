@@ -75,6 +75,22 @@ zkgpu_msm *zkgpu_msm_create(int group, const uint8_t *points, size_t n, int wind
 int zkgpu_msm_set_scalars(zkgpu_msm *h, const uint8_t *scalars, size_t n);
 int zkgpu_msm_run(zkgpu_msm *h, uint8_t *out);     /* out: 64 or 128 bytes */
 void zkgpu_msm_destroy(zkgpu_msm *h);
+/* Test entry points of the uniform-scalar (H query) path of a G1 object; they add no product behaviour.
+   zkgpu_test_msm_path: what the object decided when it was created, 24 words: one-pass sort (0 / 1), window bits c, windows W, buckets NB | the sort's shape:
+   groups, low bucket bits, index bits, entry slots a group | run length, pieces a bucket (h_maxp), 29-bit tail (0 / 1), lane exponent of the last combine | the
+   run length in effect (crowded or not), any key point at infinity, bucket arrays, result slots | the tail's shape: top, lo_bits, hi_bits, row_chunks | workgroup
+   size of the marginal kernel, its workgroups, marginal records, the flag word the last one-pass run raised (0: none; bit 0: a region or a bucket's pieces overflowed,
+   or a bucket sum was degenerate; bit 1: a degenerate sum in the tail, its result slots from bit 8 on).
+   zkgpu_test_msm_set_crowded: the longer accumulation runs a prover takes while other proofs are in flight.
+   zkgpu_test_msm_run_product: sum_i (a_i b_i z_i) P_i with the product formed inside the sort kernel (z: one element, or a table of n); canonical operands.
+   zkgpu_test_msm_h_state: what the last run left on the device — only meaningful after a run that did not fall back (zkgpu_general_path_repeats): what = 0 entries
+   per bucket, 1 where each bucket's entries start, 2 entries per group, 3 the sorted entries (groups x slots; entry = low bucket bits | sign | table index), 4 the
+   bucket sums on 29-bit limbs (48 words a bucket: X, Y, ZZ, ZZZ in slots of 12 words, nine limbs each; all-zero ZZ = the point at infinity).  *words = how
+   many words were written; an error if cap_words is too small. */
+int zkgpu_test_msm_path(zkgpu_msm *h, uint32_t out[24]);
+int zkgpu_test_msm_set_crowded(zkgpu_msm *h, int on);
+int zkgpu_test_msm_run_product(zkgpu_msm *h, const uint8_t *a, const uint8_t *b, const uint8_t *z, int z_is_table, uint8_t out[64]);
+int zkgpu_test_msm_h_state(zkgpu_msm *h, int what, uint32_t *out, size_t cap_words, size_t *words);
 
 /* ---- evaluation domains --------------------------------------------------------------------------------------------- */
 size_t zkgpu_domain_size(size_t min_size);          /* m chosen by get_evaluation_domain for this minimum size, 0 if none */

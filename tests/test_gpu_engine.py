@@ -94,17 +94,22 @@ def test_witness_msm_fast_path_edge_cases(group):
     check(o.to_arr([o.R_MOD - 1 - i for i in range(n)]))                                           # full-width values only: 32 digits each
     check(witness_like_scalars(78, n)); m.close()
 
-def test_msm_one_pass_sort_and_its_overflow_fallback():
-    """uniform-scalar hint (the H query): slots of fixed capacity per bucket; a scalar vector that piles everything into a few buckets overflows them and must
-    come out right through the two-pass fallback, and the object must keep working afterwards"""
-    n = 6000; g = o.SplitMix64(77); P = o.g1_consecutive(g.field(), n); m = e.ResidentMsm(1, P, 10, filter_ones=2)
+@pytest.mark.parametrize("c", [10, 13, 16])
+def test_msm_one_pass_sort_and_its_overflow_fallback(c):
+    """uniform-scalar hint (the H query).  Window 10 is the hinted object on the TWO-pass path (26 digits a scalar: the one-pass sort stages at most 20, so it needs a
+    window of 13 bits or more); at 13 and 16 the one-pass sort runs: regions of fixed capacity per group of buckets and pieces of fixed number per bucket; a scalar
+    vector that piles everything into a few buckets overflows them and must come out right through the two-pass fallback, and the object must keep working afterwards
+    (tests/test_gpu_msm_h_path.py takes that path apart)"""
+    n = 6000; g = o.SplitMix64(77); P = o.g1_consecutive(g.field(), n); m = e.ResidentMsm(1, P, c, filter_ones=2); assert m.path().one_pass == (c >= 13)
     K = rand_field_arr(4242, n); m.set_scalars(K); assert o.g1_from(m.run())[0] == o.msm_g1(P, K)
     same = o.to_arr([0x1234567 << 40 | 3] * n); m.set_scalars(same); assert o.g1_from(m.run())[0] == o.msm_g1(P, same)          # every digit equal: overflow
     K2 = rand_field_arr(4243, n); m.set_scalars(K2); assert o.g1_from(m.run())[0] == o.msm_g1(P, K2)
     m.close()
 
-def test_h_path_degenerate_additions_fall_back_and_stay_exact():
-    """the H query's 29-bit run accumulation (k_hacc_runs29, filter_ones=2) uses INCOMPLETE mixed additions: an operand equal to +-the accumulator leaves ZZ = 0 (mod p),
+@pytest.mark.parametrize("c", [10, 13, 16])
+def test_h_path_degenerate_additions_fall_back_and_stay_exact(c):
+    """the H query's 29-bit run accumulation (k_hacc_runs29, filter_ones=2, a window of 13 bits or more: at window 10 the hinted object takes the two-pass path, whose
+    formulas are complete) uses INCOMPLETE mixed additions: an operand equal to +-the accumulator leaves ZZ = 0 (mod p),
     which k_hacc_combine29 must notice and send to the general path (complete formulas: alt_bn128_g1.cpp:139-195 '+' with its doubling fallback, multiexp.tcc:165-282).
     Inputs a key could legally hold: repeated points with equal scalars (doubling inside a run), P / -P pairs with equal scalars (cancellation), every point equal, and a
     mixture of all three; each must give the oracle's sum and the resident object must keep working on ordinary scalars afterwards."""
@@ -112,14 +117,14 @@ def test_h_path_degenerate_additions_fall_back_and_stay_exact():
     def neg(pt):                                                                                  # (x, -y): q - y on the stored words, Montgomery form or not
         r = pt.copy(); r[4:] = o.limbs((o.Q_MOD - o.from_arr(pt)[1]) % o.Q_MOD); return r
     def run(P, S):
-        m = e.ResidentMsm(1, P, 10, filter_ones=2); m.set_scalars(S); got = o.g1_from(m.run())[0]; assert got == o.msm_g1(P, S)
+        m = e.ResidentMsm(1, P, c, filter_ones=2); assert m.path().one_pass == (c >= 13); m.set_scalars(S); got = o.g1_from(m.run())[0]; assert got == o.msm_g1(P, S)
         S2 = rand_field_arr(4106, len(P)); m.set_scalars(S2); assert o.g1_from(m.run())[0] == o.msm_g1(P, S2); m.close()        # still usable, still exact
     # (a) pairs of equal points with equal scalars: the same digit in every window, so both land in the same bucket
     P = base.copy(); S = K.copy(); P[1::2] = P[0::2]; S[1::2] = S[0::2]; run(P, S)
     # (b) P, -P with equal scalars: every bucket cancels to the point at infinity (the whole sum is the group's zero)
     P = base.copy(); S = K.copy()
     for i in range(0, 400, 2): P[i + 1] = neg(P[i]); S[i + 1] = S[i]
-    P = P[:400]; S = S[:400]; m = e.ResidentMsm(1, P, 10, filter_ones=2); m.set_scalars(S); assert o.g1_from(m.run())[0] is None and o.msm_g1(P, S) is None; m.close()
+    P = P[:400]; S = S[:400]; m = e.ResidentMsm(1, P, c, filter_ones=2); assert m.path().one_pass == (c >= 13); m.set_scalars(S); assert o.g1_from(m.run())[0] is None and o.msm_g1(P, S) is None; m.close()
     # (c) every point equal, random scalars: every bucket collision is a doubling
     P = np.repeat(base[:1], 3000, axis=0); S = K[:3000]; run(P, S)
     # (d) a mixture inside an otherwise ordinary query

@@ -27,6 +27,9 @@ def test_msm_g1_at_h_query_size_matches_oracle():
     K = np.zeros((n, 4), dtype=np.uint64); rng = np.random.default_rng(18); K[:] = rng.integers(0, 1 << 63, size=(n, 4), dtype=np.uint64) * 2 + rng.integers(0, 2, size=(n, 4), dtype=np.uint64); K[:, 3] &= np.uint64((1 << 61) - 1)
     t0 = time.time(); exp = o.msm_g1(P, K); t_o = time.time() - t0
     assert o.g1_from(e.msm(1, P, K))[0] == exp
+    # the same sum on the kernels the H query really runs: with the uniform-scalar hint (window 16 at this size) the one-pass sort and the 29-bit accumulation take
+    # it, and ordinary scalars must not send it back to the general path
+    before = e.general_path_repeats(); assert o.g1_from(e.msm(1, P, K, filter_ones=2))[0] == exp and e.general_path_repeats() == before
     n2 = 227047; sel = rng.integers(0, 1000, size=n2); Z = K[:n2].copy(); Z[sel < 509] = 0; ones = (sel >= 509) & (sel < 967); Z[ones] = 0; Z[ones, 0] = 1
     small = (sel >= 967) & (sel < 995); Z[small, 1:] = 0; Z[small, 0] &= np.uint64(0xffffffff)                      # 50.9 % zero, 45.8 % one, 3.3 % other (mostly <= 32 bit)
     t0 = time.time(); exp2 = o.msm_g1(P[:n2], Z, mixed=True); t_o += time.time() - t0
