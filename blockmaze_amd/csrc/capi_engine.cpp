@@ -263,6 +263,12 @@ int zkgpu_accts_fill(zkgpu_accts *a, const uint8_t *addrs, zk_block_record *recs
 int zkgpu_accts_commit_chain(zkgpu_accts *a, const uint8_t *addrs, const zk_block_record *recs, size_t n) { return guarded_accts(a, [&] {
   if (!a->a.commit_chain(addrs, (const uint8_t *)recs, n, nullptr)) { g_err = "account table: a null pointer, or the log would reach 2^32 - 2 entries"; return ZKGPU_ERR_ARG; }
   return ZKGPU_OK; }); }
+int zkgpu_accts_fill_segment(zkgpu_accts *a, const uint8_t *addrs, zk_block_record *recs, size_t n) { return guarded_accts(a, [&] {
+  if (!a->a.fill_segment(addrs, (uint8_t *)recs, n)) { g_err = "account table: a null pointer, or more records than the log has room for"; return ZKGPU_ERR_ARG; }
+  return ZKGPU_OK; }); }
+int zkgpu_accts_commit_segment(zkgpu_accts *a, const uint8_t *addrs, const zk_block_record *recs, size_t n) { return guarded_accts(a, [&] {
+  if (!a->a.commit_segment(addrs, (const uint8_t *)recs, n, nullptr)) { g_err = "account table: a null pointer, or the log would reach 2^32 - 2 entries"; return ZKGPU_ERR_ARG; }
+  return ZKGPU_OK; }); }
 int zkgpu_accts_rewind(zkgpu_accts *a, uint64_t size) { return guarded_accts(a, [&] {
   if (!a->a.rewind(size)) { g_err = "account table: cannot rewind to " + std::to_string(size) + " entries, the table holds fewer"; return ZKGPU_ERR_ARG; }
   return ZKGPU_OK; }); }

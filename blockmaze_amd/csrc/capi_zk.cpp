@@ -40,6 +40,7 @@
 #include "../../include/zk_tree_block.h"
 #include "../../include/zk_tree_chain.h"
 #include "../../include/zk_accounts.h"
+#include "../../include/zk_accounts_chain.h"
 #include "../../include/zkgpu.h"
 #include "blockmaze_circuits.hpp"
 #include "capi_accounts.hpp"
@@ -2088,6 +2089,74 @@ int verifyChainTree(zk_proof_cache *cache, const zk_block_record *recs, int n, c
       if (set && set_sizes) set_sizes[b] = (long long)(b < B3 ? set_at[b] : set_size);
       if (tree_sizes) tree_sizes[b] = (long long)(b < B3 ? s[b] : tree_size); }
     return B3;
+  }
+  catch (const std::exception &e) { return fail(e.what()); }
+  catch (...) { return fail("unknown error"); }
+}
+
+// ---- a stretch of the chain with accounts (DESIGN.md "A stretch of the chain with accounts"; include/zk_accounts_chain.h) ----------------------------------------
+// The loop "verifyBlockAccounts(commit = 1) block after block, stop at the first block that is not accepted whole" without the loop: one chained fill over the whole
+// segment (the tiled search), verifyChainTree on the filled records, the cut at the first rejection of the first rejected block, one append of the accepted blocks'
+// records.  The table's mutex is held only inside the two segment calls, never together with the cache's, the set's or the tree's.
+int verifyChainAccounts(zk_proof_cache *cache, zk_block_record *recs, const uint8_t (*froms)[20], int n, const int *block_first, int n_blocks, zk_accts *accts,
+                        zk_tree *tree, const long long *prior_anchors, int n_prior, int window, zk_snset *set, unsigned char *ok, int32_t *anchor_of,
+                        long long *accts_sizes, long long *set_sizes, long long *tree_sizes) {
+  auto fail = [&](const std::string &why) {
+    zkgpu_set_error(why); fprintf(stderr, "libzkgpu: verifyChainAccounts: %s\n", why.c_str());
+    for (int i = 0; i < n; i++) { if (ok) ok[i] = 0; if (anchor_of) anchor_of[i] = -1; }
+    return -1; };
+  try {
+    // 0. the arguments — verifyChainTree's among them, which it looks at again — before recs is written or anything is queued
+    if (!tree) return fail("no tree");
+    if (n < 0 || n_blocks < 0 || (n && (!recs || !ok || !froms))) return fail("a negative count or a null pointer");
+    if (!accts) return fail("no account table");
+    if (!block_first || block_first[0] != 0 || block_first[n_blocks] != n) return fail("block_first does not run from 0 to n");
+    for (int b = 0; b < n_blocks; b++) if (block_first[b] > block_first[b + 1]) return fail("block_first decreases at block " + std::to_string(b));
+    if (n_prior < 0 || (n_prior && !prior_anchors)) return fail("a negative number of prior anchors or a null pointer");
+    if (window < 0) return fail("a negative window");
+    if (!gpu_available()) return fail("no HIP device visible; libzkgpu has no CPU fallback");
+    const uint64_t tree_before = tree->t.size(), set_before = set ? set->s.size() : 0, accts_before = accts->a.size();
+    for (int a = 0; a < n_prior; a++) if (prior_anchors[a] < 0 || (uint64_t)prior_anchors[a] > tree_before) return fail("prior anchor " + std::to_string(a) + " is negative or above the tree's size");
+    { uint64_t sends = 0; for (int i = 0; i < n; i++) sends += recs[i].kind == ZK_KIND_SEND;
+      if (sends > (1ull << tree->t.depth()) - tree_before) return fail("the segment's sends do not fit into the tree"); }
+    if (accts_before + (uint64_t)n >= 0xFFFFFFFEull) return fail("the segment's records do not fit into the account table's log");
+    // 1. every record's old balance commitment from the table, chained through the whole segment
+    if (n && zkgpu_accts_fill_segment(accts, (const uint8_t *)froms, recs, (size_t)n) != ZKGPU_OK) return fail(zkgpu_last_error());
+    // 2. verifyChainTree's road on the statements as they now stand; a failure there has rewound what it did and written the failure's outputs
+    std::vector<long long> set_at((size_t)n_blocks + 1), tree_at((size_t)n_blocks + 1); std::vector<uint64_t> accts_at((size_t)n_blocks + 1, 0);   // (nothing below allocates once the set and the tree are written)
+    const int B = verifyChainTree(cache, recs, n, block_first, n_blocks, tree, prior_anchors, n_prior, window, set, ok, anchor_of, set_at.data(), tree_at.data());
+    if (B < 0) return -1;
+    // 3. the first rejected record f of the first rejected block ends the decided part: what follows it in the block was verified under an assumption that failed
+    if (B < n_blocks) {
+      int f = block_first[B]; while (f < block_first[B + 1] && ok[f]) f++;
+      for (int i = f; i < block_first[B + 1]; i++) { ok[i] = 0; if (anchor_of && i > f) anchor_of[i] = -1; }
+    }
+    // 4. the records of the accepted blocks become entries of the table, in one append; the table's size after each block follows from the records with kind <= 3
+    const int end = block_first[B];
+    { uint64_t at = accts_before;
+      for (int b = 0; b < n_blocks; b++) { if (b < B) for (int i = block_first[b]; i < block_first[b + 1]; i++) at += recs[i].kind <= 3; accts_at[b] = at; } }
+    if (end) {
+      std::string why; bool good = zkgpu_accts_commit_segment(accts, (const uint8_t *)froms, recs, (size_t)end) == ZKGPU_OK;
+      if (!good) why = zkgpu_last_error();
+      else if (accts->a.size() != (B ? accts_at[B - 1] : accts_before)) { good = false; why = "the account table's size after the call is not what the accepted records account for: another writer changed it during the call"; }
+      if (!good) {                                                                                  // 5. the set and the tree go back to their sizes before the call
+        bool back = true;
+        if (set) { try { back = set->s.rewind(set_before) && back; } catch (const std::exception &e) { back = false; fprintf(stderr, "libzkgpu: verifyChainAccounts: the spent set could not be rewound (%s)\n", e.what()); } }
+        try { back = tree->t.rewind(tree_before) && back; } catch (const std::exception &e) { back = false; fprintf(stderr, "libzkgpu: verifyChainAccounts: the tree could not be rewound (%s)\n", e.what()); }
+        if (!back && n_blocks) {                                                                    // the one -1 that may leave the set or the tree changed: the sizes as they now are
+          if (accts_sizes) accts_sizes[n_blocks - 1] = (long long)accts->a.size();
+          if (set && set_sizes) set_sizes[n_blocks - 1] = (long long)set->s.size();
+          if (tree_sizes) tree_sizes[n_blocks - 1] = (long long)tree->t.size();
+          why += "; the set or the tree could not be rewound either (the sizes after the call are reported)";
+        }
+        return fail(why);
+      }
+    }
+    for (int b = 0; b < n_blocks; b++) {
+      if (accts_sizes) accts_sizes[b] = (long long)accts_at[b];
+      if (set && set_sizes) set_sizes[b] = set_at[b];
+      if (tree_sizes) tree_sizes[b] = tree_at[b]; }
+    return B;
   }
   catch (const std::exception &e) { return fail(e.what()); }
   catch (...) { return fail("unknown error"); }

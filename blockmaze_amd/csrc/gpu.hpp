@@ -262,8 +262,12 @@ class AccountTable {
   bool get(const uint8_t *addrs, size_t q, int64_t at_size /* -1 = current */, uint8_t *out /* q x 32 */);   // read-only, one launch
   // the OLD slot of every record (and nothing else of it) becomes the sender's value: the table's current one, or — chained — the NEW slot of the closest earlier
   // record of the call with the same sender.  The table is afterwards what it was, index included.
-  bool fill(const uint8_t *addrs, uint8_t *recs, size_t n, bool chained);
-  bool commit_chain(const uint8_t *addrs, const uint8_t *recs, size_t n, uint64_t *size_out /* or null */);   // set() with the values read from the records' NEW slots
+  bool fill(const uint8_t *addrs, uint8_t *recs, size_t n, bool chained, bool tiled = false /* the segment entries: the tiled predecessor search */);
+  bool commit_chain(const uint8_t *addrs, const uint8_t *recs, size_t n, uint64_t *size_out /* or null */, bool tiled = false);   // set() with the values read from the records' NEW slots
+  // a stretch of the chain: what fill(chained) writes and what commit_chain appends, by the tiled search, whose list walks are bounded by the batch's tiles
+  // (ceil(n / 256) nodes), not by a sender's records
+  bool fill_segment(const uint8_t *addrs, uint8_t *recs, size_t n) { return fill(addrs, recs, n, true, true); }
+  bool commit_segment(const uint8_t *addrs, const uint8_t *recs, size_t n, uint64_t *size_out /* or null */) { return commit_chain(addrs, recs, n, size_out, true); }
   bool rewind(uint64_t size);                                                 // the table becomes state `size`
   bool read_log(uint64_t first, uint64_t count, uint8_t *out);                // entries first .. first + count - 1: 56 bytes each — address 20, value 32, prev as a little-endian word
   void table(std::vector<uint32_t> &slots, uint64_t &seed, uint64_t &tombstones);   // tests: the index as it lies in device memory

@@ -6,9 +6,10 @@
 // index is the spent set's table (gpu_snset.hip): 32-bit slots, a power of two of them, linear probing from the same seeded mix; a slot holds 0 (empty), 0xFFFFFFFF (a
 // tombstone, left by a rewind) or log index + 1 of the address's LATEST entry.  During one call a slot may also hold a TENTATIVE value n_old + 1 + j: record j of the
 // batch has claimed it for an address the table did not hold.  Beside the slots lies one side word a slot, `heads`: all zero between calls; during a call the head
-// (record + 1) of the list of the batch's records that ended at the slot.
+// (record + 1) of the list of the batch's records that ended at the slot — on the segment road, of the first such record of each tile of 256.
 // Rules every kernel keeps (the spent set's four):
-//   - no lane waits for another lane, wave or workgroup;
+//   - no lane waits for another lane, wave or workgroup — the one barrier, in k_acct_probe_tiled, is reached by every lane of its workgroup unconditionally, each
+//     after a bounded probe of its own, and nothing spins on memory;
 //   - every probe ends after `slots` steps, every list walk after the chain cap or the log's length, and running out sets a word of the call's head;
 //   - inside one launch slots and heads are touched by atomics only (agent-scope relaxed loads and stores, atomicCAS, atomicExch, atomicMax), and "empty" is never
 //     acted on from a load — a slot is claimed by CAS alone, never a tombstone, so a slot that is not empty stays so for the whole launch;
@@ -99,6 +100,76 @@ __global__ void __launch_bounds__(AC_THREADS) k_acct_pred(const uint32_t *__rest
     }
   }
   pred[i] = best; succ[i] = later; base[i] = b;
+}
+// ---- the tiled search (DESIGN.md "A stretch of the chain with accounts"): launches 1 and 2 of a SEGMENT batch.  A tile is a workgroup's AC_THREADS consecutive
+// records.  Inside a tile the records of one slot find each other through LDS; a slot's list holds ONE node for each tile the slot occurs in — the tile's first
+// record of it — so a walk visits at most ceil(n / AC_THREADS) nodes whatever a sender's share of the batch is.
+// Launch 1: where[i] as k_acct_probe finds it (same walk, same claim, same tentative values, same error word).  No lane returns before the barrier — the one place a
+// lane waits, which every lane of the workgroup reaches after its own bounded probe —; lanes at or beyond n take part with AC_NONE.  Then one pass over the tile's
+// 256 where words, every lane reading the same word (a broadcast): the closest lower lane with the lane's slot — pred[i], written at once — and the highest one
+// above it — the tile-last.  A lane with a higher one writes succ[i] = 1; the tile-last's succ word is left to launch 2.  A lane without a lower one is the
+// tile-first: it writes pred[i] = 0 (launch 2 knows it by that), tlast[i], and pushes itself, and only itself, on the slot's list.
+__global__ void __launch_bounds__(AC_THREADS) k_acct_probe_tiled(AcTable T, const uint32_t *__restrict__ log, uint32_t n_old, const uint32_t *__restrict__ addrs, uint32_t n,
+                                                                  uint32_t *__restrict__ where, uint32_t *__restrict__ link, uint32_t *__restrict__ pred, uint32_t *__restrict__ succ,
+                                                                  uint32_t *__restrict__ tlast, uint32_t *__restrict__ head) {
+  __shared__ __align__(16) uint32_t tile[AC_THREADS];
+  const uint32_t t = threadIdx.x, first = blockIdx.x * AC_THREADS, i = first + t; uint32_t at = AC_NONE;
+  if (i < n) {
+    const AcAddr k = ac_load(addrs + AC_ADDR * (size_t)i); const uint32_t mine = n_old + 1 + i; uint32_t s = acct_home(k, T);
+    for (uint32_t step = 0; step <= T.mask; step++, s = (s + 1) & T.mask) {
+      uint32_t v = ac_slot_load(T.slots + s);
+      if (v == 0) { v = atomicCAS(T.slots + s, 0u, mine); if (v == 0) { at = s; break; } }
+      if (v == AC_TOMB) continue;
+      if (v > n_old && v - n_old - 1 >= n) break;                                                 // no value of this call or of the table: the table is damaged
+      const AcAddr o = ac_load(v <= n_old ? log + AC_ENTRY * (size_t)(v - 1) : addrs + AC_ADDR * (size_t)(v - n_old - 1));
+      if (ac_equal(k, o)) { at = s; break; }
+    }
+    if (at == AC_NONE) head[AH_ERR] = 1;
+  }
+  tile[t] = at;
+  __syncthreads();
+  if (i >= n) return;
+  where[i] = at;
+  if (at == AC_NONE) { link[i] = 0; pred[i] = 0; succ[i] = 0; tlast[i] = i; return; }
+  uint32_t lower = 0, last = t;                                                                     // lower: lane + 1 of the closest lower lane of the slot
+  const uint4 *tile4 = reinterpret_cast<const uint4 *>(tile);                                      // four words a read: 64 LDS reads a lane, without a branch
+#pragma unroll 4
+  for (uint32_t q = 0; q < AC_THREADS / 4; q++) {
+    const uint4 v = tile4[q]; const uint32_t w4[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (uint32_t c = 0; c < 4; c++) { const uint32_t j = 4 * q + c; const bool same = w4[c] == at; lower = same && j < t ? j + 1 : lower; last = same && j > t ? j : last; }
+  }
+  if (last != t) succ[i] = 1;
+  if (lower) { pred[i] = first + lower; return; }
+  pred[i] = 0; tlast[i] = first + last;
+  link[i] = atomicExch(T.heads + at, i + 1);
+}
+// Launch 2: base[i] as k_acct_pred reads it.  Only a tile-first (pred[i] == 0 and a slot) walks the slot's list — the tile-firsts of the slot, in no order — and keeps
+// the highest node below its own and whether one above exists.  Its predecessor is the LAST record of the slot in that earlier tile, tlast[node]; and it stores "a
+// later tile holds the slot" into the succ word of its own tile's last record, which launch 1 left alone: a plain store to another record's word, read by launch 3.
+// A walk of more than `cap` nodes raises AH_OVER, as in k_acct_pred.
+__global__ void __launch_bounds__(AC_THREADS) k_acct_pred_tiled(const uint32_t *__restrict__ slots, const uint32_t *__restrict__ heads, const uint32_t *__restrict__ where,
+                                                                 const uint32_t *__restrict__ link, const uint32_t *__restrict__ tlast, uint32_t n, uint32_t n_old, uint32_t cap,
+                                                                 uint32_t *pred, uint32_t *succ, uint32_t *__restrict__ base, uint32_t *__restrict__ head) {
+  const uint32_t i = blockIdx.x * AC_THREADS + threadIdx.x; if (i >= n) return;
+  const uint32_t w = where[i]; uint32_t b = 0;
+  if (w != AC_NONE) {
+    const uint32_t v = ac_slot_load(slots + w); b = v <= n_old ? v : 0u;
+    if (pred[i] == 0) {
+      uint32_t node = ac_slot_load(heads + w), steps = 0, best = 0, later = 0; bool sound = true;
+      while (node) {
+        if (node > n) { head[AH_ERR] = 4; sound = false; break; }
+        if (steps++ == cap) { head[AH_OVER] = 1; sound = false; break; }
+        const uint32_t j = node - 1;
+        if (j < i) best = max(best, node); else if (j > i) later = 1;
+        node = link[j];
+      }
+      const uint32_t mine = tlast[i], theirs = best ? tlast[best - 1] : 0u;
+      if (sound && (mine >= n || theirs >= n)) head[AH_ERR] = 4;
+      else if (sound) { pred[i] = best ? theirs + 1 : 0u; succ[mine] = later; }                       // (not sound: launch 3 does nothing, or the call fails)
+    }
+  }
+  base[i] = b;
 }
 // Launch 3, one lane per record.  The value the address has before record i: the batch value of its predecessor (chained), else the value of the resident entry,
 // else zero.  fill (append = 0): that value goes to old[i]; the one record of a slot without a successor zeroes the slot's head and, where the slot was a claimed
@@ -230,7 +301,7 @@ struct AccountTable::Impl {
     HIP_CHECK(hipGetLastError()); HIP_CHECK(hipStreamSynchronize(gpu().stream));                  // (the old allocation is let go below)
     log = std::move(fresh); cap = c;
   }
-  template <class Gather> const uint8_t *batch(size_t m, bool append, bool chained, Gather gather);
+  template <class Gather> const uint8_t *batch(size_t m, bool append, bool chained, bool tiled, Gather gather);
 };
 
 AccountTable::AccountTable(int log2_slots, const uint64_t *seed) : impl(new Impl) {
@@ -249,14 +320,15 @@ void AccountTable::set_chain_cap(uint32_t cap) { std::lock_guard<std::mutex> lk(
 // into the pinned staging buffer, the one pass the host makes over the batch.  append: the records become log entries n .. n + m - 1; otherwise the return value
 // points at m x 32 bytes in pinned memory, each record's value before it — chained: after the earlier records of the batch —, valid until the table's next call.
 // One upload, at most one rebuild, three launches and one download whatever m is; a list beyond the chain cap adds the host's search, one upload, the third launch
-// again and one download.  The caller holds the table's mutex and has checked the arguments.
-template <class Gather> const uint8_t *AccountTable::Impl::batch(size_t m, bool append, bool chained, Gather gather) {
+// again and one download.  tiled: launches 1 and 2 are the tiled search's (the segment entries), with one more array, tlast m, at the end of the call's arrays; the
+// third launch, the host finish and everything else are the same.  The caller holds the table's mutex and has checked the arguments.
+template <class Gather> const uint8_t *AccountTable::Impl::batch(size_t m, bool append, bool chained, bool tiled, Gather gather) {
   Impl &d = *this;
   LaneScope lane(0); std::lock_guard<std::mutex> gl(g_gpu_mutex); hipStream_t s = gpu().stream;
   // a call's arrays, in words: addrs 5m | vals 8m | head | old 8m | pred m | succ m | where m | link m | base m.  Up: addrs .. head (the head arrives as zero).  Down:
   // head .. old (append: the head alone).  Pinned memory, in words: the upload | the download | pred m, succ m of a host finish — the addresses stay where they are.
   const size_t o_vals = AC_ADDR * m, o_head = o_vals + AC_VAL * m, o_old = o_head + AH_HEAD, o_pred = o_old + AC_VAL * m, o_succ = o_pred + m, o_where = o_succ + m, o_link = o_where + m, o_base = o_link + m,
-               words = o_base + m, down = AH_HEAD + (append ? 0 : AC_VAL * m);
+               o_tlast = o_base + m, words = o_tlast + (tiled ? m : 0), down = AH_HEAD + (append ? 0 : AC_VAL * m);
   const size_t up = o_head + AH_HEAD, p_down = up, p_ps = p_down + down;
   d.pinned(4 * (p_ps + 2 * m)); uint8_t *const back = d.pin + 4 * p_down;
   gather(d.pin, d.pin + 4 * o_vals); memset(d.pin + 4 * o_head, 0, 4 * AH_HEAD);
@@ -268,9 +340,15 @@ template <class Gather> const uint8_t *AccountTable::Impl::batch(size_t m, bool 
   if (lg) fresh = d.rebuilt(lg, W + o_head + AH_ERR);
   const AcTable T = lg ? d.table(fresh.slots.get(), fresh.heads.get(), lg) : d.table(); bool scratch_flag = false; Writing w(lg ? scratch_flag : d.damaged);
   const dim3 grid(cdiv(m, AC_THREADS)), block(AC_THREADS); const uint32_t *A = W, *V = W + o_vals;
-  hipLaunchKernelGGL(k_acct_probe, grid, block, 0, s, T, (const uint32_t *)d.log.get(), n_old, A, mm, W + o_where, W + o_link, W + o_head); launched();
-  hipLaunchKernelGGL(k_acct_pred, grid, block, 0, s, (const uint32_t *)T.slots, (const uint32_t *)T.heads, (const uint32_t *)(W + o_where), (const uint32_t *)(W + o_link), mm, n_old, d.chain_cap, W + o_pred, W + o_succ,
-                     W + o_base, W + o_head); launched();
+  if (tiled) {
+    hipLaunchKernelGGL(k_acct_probe_tiled, grid, block, 0, s, T, (const uint32_t *)d.log.get(), n_old, A, mm, W + o_where, W + o_link, W + o_pred, W + o_succ, W + o_tlast, W + o_head); launched();
+    hipLaunchKernelGGL(k_acct_pred_tiled, grid, block, 0, s, (const uint32_t *)T.slots, (const uint32_t *)T.heads, (const uint32_t *)(W + o_where), (const uint32_t *)(W + o_link), (const uint32_t *)(W + o_tlast), mm, n_old,
+                       d.chain_cap, W + o_pred, W + o_succ, W + o_base, W + o_head); launched();
+  } else {
+    hipLaunchKernelGGL(k_acct_probe, grid, block, 0, s, T, (const uint32_t *)d.log.get(), n_old, A, mm, W + o_where, W + o_link, W + o_head); launched();
+    hipLaunchKernelGGL(k_acct_pred, grid, block, 0, s, (const uint32_t *)T.slots, (const uint32_t *)T.heads, (const uint32_t *)(W + o_where), (const uint32_t *)(W + o_link), mm, n_old, d.chain_cap, W + o_pred, W + o_succ,
+                       W + o_base, W + o_head); launched();
+  }
   auto write = [&](int forced) {
     hipLaunchKernelGGL(k_acct_write, grid, block, 0, s, T, d.log.get(), n_old, A, V, mm, (const uint32_t *)(W + o_where), (const uint32_t *)(W + o_pred), (const uint32_t *)(W + o_succ), (const uint32_t *)(W + o_base),
                        append ? 1 : 0, chained ? 1 : 0, forced, W + o_old, (const uint32_t *)(W + o_head)); launched();
@@ -292,7 +370,7 @@ template <class Gather> const uint8_t *AccountTable::Impl::batch(size_t m, bool 
 bool AccountTable::set(const uint8_t *addrs, const uint8_t *values, size_t n, uint64_t *size_out) {
   Impl &d = *impl; std::lock_guard<std::mutex> lk(d.mu);
   if ((n && (!addrs || !values)) || n >= AC_MAX_LOG || d.n + n >= AC_MAX_LOG) return false;
-  if (n) d.batch(n, true, true, [&](uint8_t *a, uint8_t *v) { memcpy(a, addrs, 20 * n); memcpy(v, values, 32 * n); });
+  if (n) d.batch(n, true, true, false, [&](uint8_t *a, uint8_t *v) { memcpy(a, addrs, 20 * n); memcpy(v, values, 32 * n); });
   if (size_out) *size_out = d.n;
   return true;
 }
@@ -306,12 +384,12 @@ static void acct_gather(const uint8_t *addrs, const uint8_t *recs, size_t n, uin
   for (size_t i = 0, j = 0; i < n; i++) { const uint8_t *r = recs + REC_BYTES * i; if (r[0] > 3) continue;
     memcpy(a + 20 * j, addrs + 20 * i, 20); if (v) memcpy(v + 32 * j, r + REC_ARGS + 32 * acct_new_arg(r[0]), 32); j++; }
 }
-bool AccountTable::fill(const uint8_t *addrs, uint8_t *recs, size_t n, bool chained) {
+bool AccountTable::fill(const uint8_t *addrs, uint8_t *recs, size_t n, bool chained, bool tiled) {
   Impl &d = *impl; std::lock_guard<std::mutex> lk(d.mu);
   if ((n && (!addrs || !recs)) || n >= AC_MAX_LOG || d.n + n >= AC_MAX_LOG) return false;
   const size_t m = acct_taking_part(recs, n); if (!m) return true;
   const uint8_t *olds = nullptr;
-  if (chained) olds = d.batch(m, false, true, [&](uint8_t *a, uint8_t *v) { acct_gather(addrs, recs, n, a, v); });
+  if (chained) olds = d.batch(m, false, true, tiled, [&](uint8_t *a, uint8_t *v) { acct_gather(addrs, recs, n, a, v); });
   else {                                                                                           // the pool's rule: every record against the current state — one read-only launch
     LaneScope lane(0); std::lock_guard<std::mutex> gl(g_gpu_mutex); hipStream_t s = gpu().stream; d.repair();
     const size_t o_head = AC_ADDR * m, o_out = o_head + AH_HEAD; d.pinned(4 * (o_out + AC_VAL * m)); Impl::grow(d.work, o_out + AC_VAL * m); uint32_t *W = d.work.get();
@@ -324,11 +402,11 @@ bool AccountTable::fill(const uint8_t *addrs, uint8_t *recs, size_t n, bool chai
   for (size_t i = 0, j = 0; i < n; i++) { uint8_t *r = recs + REC_BYTES * i; if (r[0] <= 3) memcpy(r + REC_ARGS + 32 * acct_old_arg(r[0]), olds + 32 * j++, 32); }
   return true;
 }
-bool AccountTable::commit_chain(const uint8_t *addrs, const uint8_t *recs, size_t n, uint64_t *size_out) {
+bool AccountTable::commit_chain(const uint8_t *addrs, const uint8_t *recs, size_t n, uint64_t *size_out, bool tiled) {
   Impl &d = *impl; std::lock_guard<std::mutex> lk(d.mu);
   if ((n && (!addrs || !recs)) || n >= AC_MAX_LOG || d.n + n >= AC_MAX_LOG) return false;
   const size_t m = acct_taking_part(recs, n);
-  if (m) d.batch(m, true, true, [&](uint8_t *a, uint8_t *v) { acct_gather(addrs, recs, n, a, v); });
+  if (m) d.batch(m, true, true, tiled, [&](uint8_t *a, uint8_t *v) { acct_gather(addrs, recs, n, a, v); });
   if (size_out) *size_out = d.n;
   return true;
 }

@@ -527,6 +527,13 @@ class AccountTable:
         _check(lib().zkgpu_accts_fill(ctypes.c_void_p(self.h), ab, recs.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(n), int(bool(chained)))); return recs
     def commit_chain(self, addrs, recs):
         ab, n = _keys20(addrs); recs, ptr, nr = _recs(recs); assert n == nr; _check(lib().zkgpu_accts_commit_chain(ctypes.c_void_p(self.h), ab, ptr, ctypes.c_size_t(n)))
+    def fill_segment(self, addrs, recs):
+        """fill(chained=True) by the tiled predecessor search: for a stretch of the chain, where one sender may have any share of the records"""
+        ab, n = _keys20(addrs); recs = np.array(recs, dtype=RECORD_DTYPE, copy=True); assert recs.shape == (n,)
+        _check(lib().zkgpu_accts_fill_segment(ctypes.c_void_p(self.h), ab, recs.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(n))); return recs
+    def commit_segment(self, addrs, recs):
+        """commit_chain by the tiled predecessor search"""
+        ab, n = _keys20(addrs); recs, ptr, nr = _recs(recs); assert n == nr; _check(lib().zkgpu_accts_commit_segment(ctypes.c_void_p(self.h), ab, ptr, ctypes.c_size_t(n)))
     def rewind(self, size): _check(lib().zkgpu_accts_rewind(ctypes.c_void_p(self.h), ctypes.c_uint64(size)))
     def read_log(self, first=0, count=None):
         """-> [(20-byte address, 32-byte value, prev)] of log entries first .. first + count - 1 (count None: to the end)"""
@@ -799,5 +806,17 @@ class Zk:
                                         an.ctypes.data_as(ctypes.c_void_p) if na else None, na, ctypes.c_void_p(s) if s else None, int(bool(commit)), ok, of, ctypes.byref(asize), ctypes.byref(size), ctypes.byref(tsize))
         return (rc, [bool(ok[i]) for i in range(n)], [int(of[i]) for i in range(n)], recs, (None if asize.value == -7 else int(asize.value)), (None if size.value == -7 else int(size.value)),
                 (None if tsize.value < 0 else int(tsize.value)))
+    # include/zk_accounts_chain.h: a stretch of the chain decided against the resident account table, tree and set
+    def VerifyChainAccounts(self, cache, items, froms, block_first, a, tree, prior_anchors, window, s):
+        """-> (blocks accepted or -1, [bool], [anchor_of], the records with the segment-wide chained fill, [table size after block b] or None, [set size after block b]
+        or None, [tree size after block b] or None)"""
+        recs = items if isinstance(items, np.ndarray) else records_from_items(items); recs = np.array(recs, dtype=RECORD_DTYPE, copy=True); n = int(recs.shape[0]); fb, nf = _keys20(froms); assert nf == n
+        bf = np.ascontiguousarray(block_first, dtype=np.int32).reshape(-1); nb = int(bf.size) - 1; pa = np.ascontiguousarray(prior_anchors if prior_anchors is not None else [], dtype=np.int64).reshape(-1); npa = int(pa.size)
+        ok = (ctypes.c_ubyte * max(1, n))(); of = (ctypes.c_int32 * max(1, n))(*([-7] * max(1, n))); sizes = [np.full(max(1, nb), -7, dtype=np.int64) for _ in range(3)]; self.L.verifyChainAccounts.restype = ctypes.c_int
+        rc = self.L.verifyChainAccounts(_cache_handle(cache), recs.ctypes.data_as(ctypes.c_void_p), fb if n else None, n, bf.ctypes.data_as(ctypes.c_void_p) if nb >= 0 else None, nb, _accts_handle(a),
+                                        ctypes.c_void_p(tree) if tree else None, pa.ctypes.data_as(ctypes.c_void_p) if npa else None, npa, int(window), ctypes.c_void_p(s) if s else None, ok, of,
+                                        *[x.ctypes.data_as(ctypes.c_void_p) for x in sizes])
+        out = [[int(x) for x in v[:nb]] if rc >= 0 else None for v in sizes]
+        return (rc, [bool(ok[i]) for i in range(n)], [int(of[i]) for i in range(n)], recs, out[0], (out[1] if s else None), out[2])
     def VerifyDepositProofDepth(self, depth, proof, RT, pk, cmtb_old, sn_old, cmtb, sns):
         return bool(self.L.verifyDepositproofDepth(int(depth), proof.encode(), self.hx(RT), self.hx(pk), self.hx(cmtb_old), self.hx(sn_old), self.hx(cmtb), self.hx(sns)))

@@ -377,6 +377,13 @@ int zkgpu_accts_get(zkgpu_accts *a, const uint8_t *addrs, size_t n, int64_t at_s
 int zkgpu_accts_fill(zkgpu_accts *a, const uint8_t *addrs, zk_block_record *recs, size_t n, int chained);
 /* zkgpu_accts_set with the values read from the NEW slots of the records with kind <= 3; the others add nothing */
 int zkgpu_accts_commit_chain(zkgpu_accts *a, const uint8_t *addrs, const zk_block_record *recs, size_t n);
+/* A stretch of the chain (DESIGN.md "A stretch of the chain with accounts"; the drop-in level is zk_accounts_chain.h).  fill_segment writes what zkgpu_accts_fill
+ * with chained = 1 writes, commit_segment appends what zkgpu_accts_commit_chain appends; both find a record's predecessor by the tiled search: records of one
+ * address meet inside their tile of 256 records, and an address's list holds one node for each tile it occurs in.  Three launches; a list walk visits at most
+ * ceil(m / 256) nodes for the m records with kind <= 3, so with the default chain cap no call of up to 65,536 such records takes the host's search, however many of
+ * them one address has. */
+int zkgpu_accts_fill_segment(zkgpu_accts *a, const uint8_t *addrs, zk_block_record *recs, size_t n);
+int zkgpu_accts_commit_segment(zkgpu_accts *a, const uint8_t *addrs, const zk_block_record *recs, size_t n);
 int zkgpu_accts_rewind(zkgpu_accts *a, uint64_t size);                       /* the table becomes state `size`; size 0 empties it */
 int zkgpu_accts_read_log(zkgpu_accts *a, uint64_t first, uint64_t count, uint8_t *entries /* count x 56: address, value, prev as a little-endian word */);
 /* test entries: a table of 2^log2_slots slots (4 .. 31; it still grows) with a given seed; the index as it lies in device memory (as zkgpu_test_snset_slots); the
