@@ -78,6 +78,32 @@ def point29_op(op, a, b=None):
     out = np.zeros((n, wo), dtype=np.uint32); flags = np.zeros(n, dtype=np.uint32)
     _check(lib().zkgpu_test_point29_op(code, _u32(a), _u32(b), _u32(out), _u32(flags), ctypes.c_size_t(n))); return out, flags
 
+# secp256k1 test entries (csrc/gpu_senders.hip): Python integers in and out, 32 big-endian bytes a value on the way
+SECP_OPS = {"fq_mul": 0, "fq_sqr": 1, "fq_add": 2, "fq_sub": 3, "fq_neg": 4, "fq_inv": 5, "fq_sqrt": 6, "fq_reduce": 7, "n_mul": 8, "n_inv": 9, "n_reduce": 10}
+def _be32(vals): return np.frombuffer(b"".join(int(v).to_bytes(32, "big") for v in vals), dtype=np.uint8).copy() if len(vals) else np.zeros(0, dtype=np.uint8)
+def _ints32(buf): b = bytes(buf); return [int.from_bytes(b[k:k + 32], "big") for k in range(0, len(b), 32)]
+def secp_ops(op, a, b=None):
+    """out[i] = op(a[i], b[i]) on the device, one lane a pair"""
+    n = len(a); aa = _be32(a); bb = _be32(b) if b is not None else None; assert b is None or len(b) == n; out = np.zeros(32 * n, dtype=np.uint8)
+    _check(lib().zkgpu_test_secp_ops(SECP_OPS[op], _bytes(aa), _bytes(bb) if bb is not None else None, ctypes.c_size_t(n), _bytes(out))); return _ints32(out)
+def secp_lincomb(u1, u2, points):
+    """u1[i] G + u2[i] points[i] through the recovery's own launches -> [(x, y) or None for the point at infinity]"""
+    n = len(u1); assert len(u2) == n and len(points) == n; out = np.zeros(64 * n, dtype=np.uint8); inf = np.zeros(max(1, n), dtype=np.uint8)
+    _check(lib().zkgpu_test_secp_lincomb(_bytes(_be32(u1)), _bytes(_be32(u2)), _bytes(_be32([p[0] for p in points])), _bytes(_be32([p[1] for p in points])), ctypes.c_size_t(n), _bytes(out), _bytes(inf)))
+    v = _ints32(out); return [None if inf[i] else (v[2 * i], v[2 * i + 1]) for i in range(n)]
+def secp_gtable():
+    """the resident table of G: [(x, y) of k G for k = 1 .. 15]"""
+    out = np.zeros(15 * 64, dtype=np.uint8); _check(lib().zkgpu_test_secp_gtable(_bytes(out))); v = _ints32(out); return [(v[2 * k], v[2 * k + 1]) for k in range(15)]
+def senders_counters():
+    """the last recovery or lincomb call: {equal, opposite, at_infinity, to_infinity}: lanes x times the walk's point addition took each exceptional branch"""
+    out = (ctypes.c_uint64 * 4)(); _check(lib().zkgpu_test_senders_counters(out)); return dict(zip(("equal", "opposite", "at_infinity", "to_infinity"), (int(x) for x in out)))
+def recover_senders(hashes, sigs, homestead=True, want_pubs=True):
+    """zkgpu_recover_senders -> (count or a ZKGPU_ERR_* code, froms (n, 20) uint8, pubs (n, 64) uint8 or None, ok (n,) uint8)"""
+    hb = np.frombuffer(b"".join(bytes(h) for h in hashes), dtype=np.uint8).reshape(-1, 32).copy(); sb = np.frombuffer(b"".join(bytes(x) for x in sigs), dtype=np.uint8).reshape(-1, 65).copy()
+    n = int(hb.shape[0]); assert sb.shape[0] == n; froms = np.full((n, 20), 0xA5, dtype=np.uint8); pubs = np.full((n, 64), 0xA5, dtype=np.uint8) if want_pubs else None; ok = np.full(n, 0xA5, dtype=np.uint8)
+    rc = int(lib().zkgpu_recover_senders(_bytes(hb) if n else None, _bytes(sb) if n else None, n, int(bool(homestead)), _bytes(froms) if n else None, _bytes(pubs) if (want_pubs and n) else None, _bytes(ok) if n else None))
+    return rc, froms, pubs, ok
+
 def msm(group, points, scalars, window_bits=0, filter_ones=False):
     points = np.ascontiguousarray(points, dtype=np.uint64); scalars = np.ascontiguousarray(scalars, dtype=np.uint64); n = scalars.size // 4
     out = np.zeros(8 if group == 1 else 16, dtype=np.uint64)
@@ -818,5 +844,16 @@ class Zk:
                                         *[x.ctypes.data_as(ctypes.c_void_p) for x in sizes])
         out = [[int(x) for x in v[:nb]] if rc >= 0 else None for v in sizes]
         return (rc, [bool(ok[i]) for i in range(n)], [int(of[i]) for i in range(n)], recs, out[0], (out[1] if s else None), out[2])
+    # include/zk_senders.h: the senders of n transactions from their signatures, on the device
+    def RecoverSenders(self, hashes, sigs, homestead=True, want_pubs=True):
+        """hashes: n x 32 bytes; sigs: n x 65 bytes (R || S || V).  -> (froms: [20 bytes], pubs: [64 bytes] or None, ok: [bool]); raises ZkGpuError where the call
+        returns -1"""
+        hb = np.frombuffer(b"".join(bytes(h) for h in hashes), dtype=np.uint8).reshape(-1, 32).copy(); sb = np.frombuffer(b"".join(bytes(x) for x in sigs), dtype=np.uint8).reshape(-1, 65).copy()
+        n = int(hb.shape[0]); assert sb.shape[0] == n; froms = np.zeros((max(1, n), 20), dtype=np.uint8); pubs = np.zeros((max(1, n), 64), dtype=np.uint8) if want_pubs else None; ok = np.zeros(max(1, n), dtype=np.uint8)
+        self.L.zkRecoverSenders.restype = ctypes.c_int
+        rc = int(self.L.zkRecoverSenders(_bytes(hb), _bytes(sb), n, int(bool(homestead)), _bytes(froms), _bytes(pubs) if want_pubs else None, _bytes(ok)))
+        if rc < 0: raise ZkGpuError("zkRecoverSenders: %s" % self.L.zkgpu_last_error().decode())
+        assert rc == int(ok[:n].sum())
+        return [bytes(froms[i]) for i in range(n)], ([bytes(pubs[i]) for i in range(n)] if want_pubs else None), [bool(ok[i]) for i in range(n)]
     def VerifyDepositProofDepth(self, depth, proof, RT, pk, cmtb_old, sn_old, cmtb, sns):
         return bool(self.L.verifyDepositproofDepth(int(depth), proof.encode(), self.hx(RT), self.hx(pk), self.hx(cmtb_old), self.hx(sn_old), self.hx(cmtb), self.hx(sns)))

@@ -394,6 +394,28 @@ int zkgpu_test_accts_slots(zkgpu_accts *a, uint32_t *slots, uint64_t *n_slots, u
 int zkgpu_test_accts_chain_cap(zkgpu_accts *a, uint32_t cap);
 int zkgpu_test_accts_launches(uint64_t *launches, uint64_t *host_finishes);
 
+/* ---- senders from signatures (DESIGN.md "Senders from signatures"; the drop-in level is zk_senders.h) --------------------------------------------------------
+ * secp256k1 public-key recovery and the Keccak-256 address, one lane a signature, six launches a call: the checks and R's y, the scalars u1 = -m / r and u2 = s / r,
+ * 1 R ... 15 R, the walk u1 G + u2 R over 64 windows of 4 bits, the affine key, the address.  1 G ... 15 G lie in a table built once.  One upload of 97 bytes a
+ * record and one download of 85 (21 without pubs), through pinned staging; the workspace is kept and grown.
+ * zkgpu_recover_senders takes zkRecoverSenders' arguments (as flat arrays) and returns the number of records with ok = 1, or ZKGPU_ERR_ARG (n < 0, a null pointer
+ * with n > 0; decided first, before the device is asked for, so it wins over the next), ZKGPU_ERR_NO_DEVICE (there is no host path), ZKGPU_ERR_RUNTIME; every
+ * output is zeroed on each of them. */
+int zkgpu_recover_senders(const uint8_t *sighash /* n x 32 */, const uint8_t *sigs /* n x 65 */, int n, int homestead, uint8_t *froms /* n x 20 */, uint8_t *pubs /* n x 64, or NULL */,
+                          unsigned char *ok);
+/* test entries.  Every value is 32 big-endian bytes.
+ * secp_ops: out[i] = op(a[i], b[i]), one lane a pair; op: 0 mul, 1 sqr, 2 add, 3 sub, 4 neg, 5 inv, 6 sqrt (a^((p+1)/4)), 7 reduce in the field; 8 mul, 9 inv,
+ *   10 reduce mod N.  b may be NULL for the operations of one operand.  mul, sqr and reduce take any 256-bit value; the others canonical values (secp256k1.cuh).
+ * secp_lincomb: u1[i] G + u2[i] P[i] through the launches of the recovery (the table of P, the walk, the affine step); u1, u2 below N, P = (px, py) on the curve;
+ *   out_xy[i] = X || Y, zero where out_inf[i] = 1.
+ * secp_gtable: the resident table as it lies in device memory, k G = X || Y at out + 64 (k - 1), k = 1 .. 15.
+ * senders_counters: for the last recovery or lincomb call, how many times a lane of the walk took each exceptional branch of the point addition: out = {equal
+ *   operands, opposite operands, the running sum at infinity, result at infinity}. */
+int zkgpu_test_secp_ops(int op, const uint8_t *a, const uint8_t *b, size_t n, uint8_t *out);
+int zkgpu_test_secp_lincomb(const uint8_t *u1, const uint8_t *u2, const uint8_t *px, const uint8_t *py, size_t n, uint8_t *out_xy, uint8_t *out_inf);
+int zkgpu_test_secp_gtable(uint8_t out[15 * 64]);
+int zkgpu_test_senders_counters(uint64_t out[4]);
+
 #ifdef __cplusplus
 }
 #endif
