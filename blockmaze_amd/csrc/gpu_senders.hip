@@ -188,6 +188,13 @@ struct Senders {                                     // one a process, every mem
     hipLaunchKernelGGL(k_secp_address, grid, block, 0, s, nn, W, (uint8_t *)(out + SP_HEAD), out + SP_HEAD + okw, want_pubs ? out + SP_HEAD + okw + 5 * n : (uint32_t *)nullptr);
     HIP_CHECK(hipGetLastError());
   }
+  // the recovery on records that lie on the device: hash 8 words a record, R || S 16 words, V one byte; lift, scalars, then the tail.  Queues only.
+  void body(size_t n, const uint32_t *hash, const uint32_t *rs, const uint8_t *v, bool homestead, const Ws &W, uint32_t *out, bool want_pubs, hipStream_t s) {
+    const dim3 grid(cdiv(n, SP_THREADS)), block(SP_THREADS);
+    hipLaunchKernelGGL(k_secp_lift, grid, block, 0, s, rs, v, (uint32_t)n, homestead ? 1 : 0, W);
+    hipLaunchKernelGGL(k_secp_scalars, grid, block, 0, s, hash, rs, (uint32_t)n, W);
+    tail(n, W, out, want_pubs, s);
+  }
   void keep_counters(const uint8_t *back) { uint32_t h[SP_HEAD]; memcpy(h, back, sizeof h); for (int k = 0; k < 4; k++) counters[k] = h[k]; }
 };
 Senders &senders() { static Senders *s = new Senders; return *s; }   // (never destroyed: the runtime may be gone when statics are)
@@ -207,16 +214,23 @@ size_t recover_senders(const uint8_t *sighash, const uint8_t *sigs, size_t n, bo
   Senders::grow(d.io, up + down); uint32_t *in = d.io.get(), *out = in + up;
   Senders::SyncAtExit sync; const Ws W = d.prepare(n, s);
   HIP_CHECK(hipMemcpyAsync(in, pu, 4 * up, hipMemcpyHostToDevice, s));
-  const dim3 grid(cdiv(n, SP_THREADS)), block(SP_THREADS);
-  hipLaunchKernelGGL(k_secp_lift, grid, block, 0, s, (const uint32_t *)(in + 8 * n), (const uint8_t *)(in + 24 * n), (uint32_t)n, homestead ? 1 : 0, W);
-  hipLaunchKernelGGL(k_secp_scalars, grid, block, 0, s, (const uint32_t *)in, (const uint32_t *)(in + 8 * n), (uint32_t)n, W);
-  d.tail(n, W, out, pubs != nullptr, s);
+  d.body(n, in, in + 8 * n, (const uint8_t *)(in + 24 * n), homestead, W, out, pubs != nullptr, s);
   HIP_CHECK(hipMemcpyAsync(back, out, 4 * down, hipMemcpyDeviceToHost, s)); HIP_CHECK(hipStreamSynchronize(s));
   d.keep_counters(back);
   const uint8_t *bok = back + 4 * SP_HEAD; memcpy(ok, bok, n); memcpy(froms, bok + 4 * okw, 20 * n); if (pubs) memcpy(pubs, bok + 4 * okw + 20 * n, 64 * n);
   size_t good = 0; for (size_t i = 0; i < n; i++) good += ok[i] != 0;
   return good;
 }
+// The same six launches on records another routine left on the device (gpu_txs.hip): hash n x 8 words, rs n x 16 words, v n bytes, all big-endian bytes in memory
+// order.  out: recover_senders_out_words(n) words: the head | ok n bytes (padded to words) | froms 5n.  Queues on s and returns; the caller holds the device mutex,
+// synchronises, and hands the head to senders_keep_head.
+size_t recover_senders_out_words(size_t n) { return SP_HEAD + (n + 3) / 4 + 5 * n; }
+void recover_senders_queue(const uint32_t *hash, const uint32_t *rs, const uint8_t *v, size_t n, bool homestead, uint32_t *out, hipStream_t s) {
+  if (!n) return;
+  if (n > 0x7FFFFFFFu) throw GpuError("senders: more than 2^31 - 1 records");
+  Senders &d = senders(); const Ws W = d.prepare(n, s); d.body(n, hash, rs, v, homestead, W, out, false, s);
+}
+void senders_keep_head(const uint32_t *head) { senders().keep_counters((const uint8_t *)head); }
 // u1 G + u2 P through the launches of the recovery from k_secp_rtable on: 32 big-endian bytes a value; out_xy n x 64, zero where out_inf[i] = 1
 void probe_secp_lincomb(const uint8_t *u1, const uint8_t *u2, const uint8_t *px, const uint8_t *py, size_t n, uint8_t *out_xy, uint8_t *out_inf) {
   if (!n) return;

@@ -104,6 +104,32 @@ def recover_senders(hashes, sigs, homestead=True, want_pubs=True):
     rc = int(lib().zkgpu_recover_senders(_bytes(hb) if n else None, _bytes(sb) if n else None, n, int(bool(homestead)), _bytes(froms) if n else None, _bytes(pubs) if (want_pubs and n) else None, _bytes(ok) if n else None))
     return rc, froms, pubs, ok
 
+# sender inputs from raw transactions (csrc/gpu_txs.hip; include/zk_txs.h)
+SIGNER_FRONTIER, SIGNER_HOMESTEAD, SIGNER_EIP155 = 0, 1, 2
+TX_OK, TX_MALFORMED, TX_CHAIN_ID, TX_SIG = 0, 1, 2, 3
+def _tx_blob(txs):
+    """a list of byte strings -> (the bytes end to end (at least one byte, so that the pointer is never null), off (n + 1) uint64)"""
+    raw = [bytes(t) for t in txs]; off = np.zeros(len(raw) + 1, dtype=np.uint64); off[1:] = np.cumsum([len(t) for t in raw], dtype=np.uint64) if raw else []
+    return np.frombuffer(b"".join(raw) or b"\0", dtype=np.uint8).copy(), off
+def _u64p(a): return a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+def keccak256(msgs):
+    """Keccak-256 of every byte string of msgs through the device's multi-block sponge -> [32 bytes]"""
+    n = len(msgs); blob, off = _tx_blob(msgs); out = np.zeros((max(1, n), 32), dtype=np.uint8)
+    _check(lib().zkgpu_test_keccak256(_bytes(blob), _u64p(off), ctypes.c_size_t(n), _bytes(out))); return [bytes(out[i]) for i in range(n)]
+def tx_signing_inputs(txs, signer, chain_id):
+    """zkgpu_tx_signing_inputs -> (count or a ZKGPU_ERR_* code, dict of txhash (n, 32), sighash (n, 32), sigs (n, 65), deposit_from (n, 20), code (n,), status (n,), uint8)"""
+    n = len(txs); blob, off = _tx_blob(txs); o = {k: np.full((n, w) if w else n, 0xA5, dtype=np.uint8) for k, w in (("txhash", 32), ("sighash", 32), ("sigs", 65), ("deposit_from", 20), ("code", 0), ("status", 0))}
+    p = lambda k: _bytes(o[k]) if n else None
+    rc = int(lib().zkgpu_tx_signing_inputs(_bytes(blob), _u64p(off), n, int(signer), ctypes.c_uint64(chain_id), p("txhash"), p("sighash"), p("sigs"), p("deposit_from"), p("code"), p("status")))
+    return rc, o
+def tx_senders(txs, signer, chain_id, want_txhash=True):
+    """zkgpu_tx_senders -> (count or a ZKGPU_ERR_* code, dict of txhash (n, 32) or None, froms (n, 20), code (n,), status (n,), uint8)"""
+    n = len(txs); blob, off = _tx_blob(txs); o = {k: np.full((n, w) if w else n, 0xA5, dtype=np.uint8) for k, w in (("txhash", 32), ("froms", 20), ("code", 0), ("status", 0))}
+    if not want_txhash: o["txhash"] = None
+    p = lambda k: _bytes(o[k]) if (n and o[k] is not None) else None
+    rc = int(lib().zkgpu_tx_senders(_bytes(blob), _u64p(off), n, int(signer), ctypes.c_uint64(chain_id), p("txhash"), p("froms"), p("code"), p("status")))
+    return rc, o
+
 def msm(group, points, scalars, window_bits=0, filter_ones=False):
     points = np.ascontiguousarray(points, dtype=np.uint64); scalars = np.ascontiguousarray(scalars, dtype=np.uint64); n = scalars.size // 4
     out = np.zeros(8 if group == 1 else 16, dtype=np.uint64)
@@ -855,5 +881,24 @@ class Zk:
         if rc < 0: raise ZkGpuError("zkRecoverSenders: %s" % self.L.zkgpu_last_error().decode())
         assert rc == int(ok[:n].sum())
         return [bytes(froms[i]) for i in range(n)], ([bytes(pubs[i]) for i in range(n)] if want_pubs else None), [bool(ok[i]) for i in range(n)]
+    # include/zk_txs.h: the recovery's inputs, or the senders themselves, from the raw transactions of a block body
+    def TxSigningInputs(self, txs, signer, chain_id):
+        """txs: n byte strings, one RLP transaction each.  -> (txhash: [32 bytes], sighash: [32 bytes], sigs: [65 bytes], deposit_from: [20 bytes], code: [int], status: [int]);
+        raises ZkGpuError where the call returns -1"""
+        n = len(txs); blob, off = _tx_blob(txs); o = [np.zeros((max(1, n), w), dtype=np.uint8) for w in (32, 32, 65, 20, 1, 1)]
+        self.L.zkTxSigningInputs.restype = ctypes.c_int
+        rc = int(self.L.zkTxSigningInputs(_bytes(blob), _u64p(off), n, int(signer), ctypes.c_uint64(chain_id), *[_bytes(a) for a in o]))
+        if rc < 0: raise ZkGpuError("zkTxSigningInputs: %s" % self.L.zkgpu_last_error().decode())
+        assert rc == int((o[5][:n, 0] == TX_OK).sum())
+        return tuple([bytes(a[i]) for i in range(n)] for a in o[:4]) + tuple([int(a[i, 0]) for i in range(n)] for a in o[4:])
+    def TxSenders(self, txs, signer, chain_id, want_txhash=True):
+        """-> (froms: [20 bytes], txhash: [32 bytes] or None, code: [int], status: [int]); froms goes into VerifyChainAccounts as it is.  Raises ZkGpuError where the call
+        returns -1"""
+        n = len(txs); blob, off = _tx_blob(txs); th, fr, code, st = [np.zeros((max(1, n), w), dtype=np.uint8) for w in (32, 20, 1, 1)]
+        self.L.zkTxSenders.restype = ctypes.c_int
+        rc = int(self.L.zkTxSenders(_bytes(blob), _u64p(off), n, int(signer), ctypes.c_uint64(chain_id), _bytes(th) if want_txhash else None, _bytes(fr), _bytes(code), _bytes(st)))
+        if rc < 0: raise ZkGpuError("zkTxSenders: %s" % self.L.zkgpu_last_error().decode())
+        assert rc == int((st[:n, 0] == TX_OK).sum())
+        return [bytes(fr[i]) for i in range(n)], ([bytes(th[i]) for i in range(n)] if want_txhash else None), [int(code[i, 0]) for i in range(n)], [int(st[i, 0]) for i in range(n)]
     def VerifyDepositProofDepth(self, depth, proof, RT, pk, cmtb_old, sn_old, cmtb, sns):
         return bool(self.L.verifyDepositproofDepth(int(depth), proof.encode(), self.hx(RT), self.hx(pk), self.hx(cmtb_old), self.hx(sn_old), self.hx(cmtb), self.hx(sns)))

@@ -416,6 +416,21 @@ int zkgpu_test_secp_lincomb(const uint8_t *u1, const uint8_t *u2, const uint8_t 
 int zkgpu_test_secp_gtable(uint8_t out[15 * 64]);
 int zkgpu_test_senders_counters(uint64_t out[4]);
 
+/* ---- sender inputs from raw transactions (the drop-in level is zk_txs.h) ------------------------------------------------------------------------
+ * One lane a transaction: k_tx_walk applies the strict RLP decoder's rules to the 26 fields of txdata and leaves a descriptor, R || S and V's byte; k_tx_hash
+ * computes the signing hash and the transaction hash (Keccak-256, multi-block sponge over a segmented byte source); zkgpu_tx_senders then runs the recovery's six
+ * launches on what lies on the device, and k_tx_finish merges the verdicts.  One upload (txs, then off) and one download, through pinned staging; the workspace
+ * is kept and grown.
+ * Both take the arguments of zkTxSigningInputs / zkTxSenders (as flat arrays) and return the number of records with status ZK_TX_OK, or ZKGPU_ERR_ARG (n < 0, a
+ * null pointer with n > 0, a decreasing off, an unknown signer, chain_id >= 2^62; decided first, before the device is asked for, so it wins over the next),
+ * ZKGPU_ERR_NO_DEVICE (there is no host path), ZKGPU_ERR_RUNTIME; every output is zeroed on each of them.  deposit_from and zkgpu_tx_senders' txhash may be NULL. */
+int zkgpu_tx_signing_inputs(const uint8_t *txs, const uint64_t *off /* n + 1 */, int n, int signer, uint64_t chain_id, uint8_t *txhash /* n x 32 */, uint8_t *sighash /* n x 32 */,
+                            uint8_t *sigs /* n x 65 */, uint8_t *deposit_from /* n x 20, or NULL */, uint8_t *code, uint8_t *status);
+int zkgpu_tx_senders(const uint8_t *txs, const uint64_t *off /* n + 1 */, int n, int signer, uint64_t chain_id, uint8_t *txhash /* n x 32, or NULL */, uint8_t *froms /* n x 20 */,
+                     uint8_t *code, uint8_t *status);
+/* test entry: out[i] = Keccak-256 (padding 0x01 ... 0x80, rate 136) of msgs[off[i] .. off[i+1]), n strings through k_tx_hash's sponge, one lane a string */
+int zkgpu_test_keccak256(const uint8_t *msgs, const uint64_t *off, size_t n, uint8_t *out /* n x 32 */);
+
 #ifdef __cplusplus
 }
 #endif
