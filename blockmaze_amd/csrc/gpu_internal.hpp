@@ -1,7 +1,8 @@
-// Shared by the HIP translation units of libzkgpu (gpu.hip, gpu_msm_g1.hip, gpu_msm_g2.hip, gpu_keyops.hip): device context, error macro, scan helper, stage
-// timer.
+// Shared by the HIP translation units of libzkgpu (gpu.hip, gpu_msm_g1.hip, gpu_msm_g2.hip, gpu_keyops.hip): device context, error macro, staging helpers, scan
+// helper, stage timer.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <atomic>
 #include <cstdlib>
 #include <map>
@@ -71,6 +72,19 @@ class GpuContext {
 };
 GpuContext &gpu();
 static inline unsigned cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
+// Staging helpers of the entries that work on the main stream.  SyncAtExit: the stream is synchronised when the entry returns or throws, so nothing reads pinned or
+// caller memory, or writes a host array, after that.
+struct SyncAtExit { ~SyncAtExit() { (void)hipStreamSynchronize(gpu().stream); } };
+// pinned host memory kept and grown by its owner: pinned(bytes) leaves at least `bytes` at `pin`, twice the request when it has to allocate, the old block freed first
+struct PinnedStage {
+  uint8_t *pin = nullptr; size_t pin_bytes = 0;
+  PinnedStage() = default; PinnedStage(const PinnedStage &) = delete; PinnedStage &operator=(const PinnedStage &) = delete;
+  ~PinnedStage() { if (pin) (void)hipHostFree(pin); }
+  void pinned(size_t bytes) { if (pin_bytes >= bytes) return; if (pin) { (void)hipHostFree(pin); pin = nullptr; pin_bytes = 0; }
+    HIP_CHECK(hipHostMalloc((void **)&pin, 2 * bytes)); pin_bytes = 2 * bytes; }
+};
+// a device workspace kept and grown: at least `count` elements, at least doubling (the contents are not kept)
+template <class T> void grow_buf(DevBuf<T> &b, size_t count) { if (b.size() < count) b = DevBuf<T>(std::max(count, 2 * b.size())); }
 // optional HIP-event timing of a pipeline stage (bench.py's roofline leg)
 struct Stage { size_t id; explicit Stage(const char *n, hipStream_t st = nullptr); ~Stage(); };
 

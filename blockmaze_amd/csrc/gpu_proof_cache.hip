@@ -67,7 +67,6 @@ uint64_t record_digest_launches() { return g_digest_launches.load(); }
 namespace {
 struct DigestWorkspace { DevBuf<uint8_t> in /* the four states, then the records */, out; size_t cap = 0; };
 DigestWorkspace &digest_workspace() { static DigestWorkspace *w = new DigestWorkspace(); return *w; }
-struct SyncAtExit { ~SyncAtExit() { (void)hipStreamSynchronize(gpu().stream); } };   // nothing reads caller memory once the entry has returned or thrown
 }  // namespace
 
 void record_digests_dev(const uint8_t *recs, size_t n, const uint32_t mid[32], uint32_t kinds, uint8_t *out20) {

@@ -161,14 +161,9 @@ __global__ void __launch_bounds__(SP_THREADS) k_secp_op(int op, const uint32_t *
 
 // ---- the host side ------------------------------------------------------------------------------------------------------------------------------------------------
 namespace {
-struct Senders {                                     // one a process, every member under the device mutex
+struct Senders : PinnedStage {                       // one a process, every member under the device mutex
   DevBuf<uint32_t> gtab, work, io; size_t stride = 0; bool table_built = false;
-  uint8_t *pin = nullptr; size_t pin_bytes = 0; uint64_t counters[4] = {0, 0, 0, 0};
-  ~Senders() { if (pin) (void)hipHostFree(pin); }
-  struct SyncAtExit { ~SyncAtExit() { (void)hipStreamSynchronize(gpu().stream); } };   // nothing reads pinned or caller memory once an entry has returned or thrown
-  void pinned(size_t bytes) { if (pin_bytes >= bytes) return; if (pin) { (void)hipHostFree(pin); pin = nullptr; pin_bytes = 0; }
-    HIP_CHECK(hipHostMalloc((void **)&pin, 2 * bytes)); pin_bytes = 2 * bytes; }
-  static void grow(DevBuf<uint32_t> &b, size_t words) { if (b.size() < words) b = DevBuf<uint32_t>(std::max(words, 2 * b.size())); }
+  uint64_t counters[4] = {0, 0, 0, 0};
   // the workspace for n lanes (kept and grown; the stride a multiple of 64, so that a wave's 64 words start on a 256-byte line) and the table of G
   Ws prepare(size_t n, hipStream_t s) {
     if (!table_built) { gtab = DevBuf<uint32_t>(15 * 16); hipLaunchKernelGGL(k_secp_gtable, dim3(1), dim3(64), 0, s, gtab.get()); HIP_CHECK(hipGetLastError());
@@ -211,8 +206,8 @@ size_t recover_senders(const uint8_t *sighash, const uint8_t *sigs, size_t n, bo
   d.pinned(4 * (up + down)); uint8_t *const pu = d.pin, *const back = d.pin + 4 * up;
   memcpy(pu, sighash, 32 * n); uint8_t *prs = pu + 32 * n, *pv = pu + 96 * n; memset(pv, 0, 4 * okw);
   for (size_t i = 0; i < n; i++) { memcpy(prs + 64 * i, sigs + 65 * i, 64); pv[i] = sigs[65 * i + 64]; }
-  Senders::grow(d.io, up + down); uint32_t *in = d.io.get(), *out = in + up;
-  Senders::SyncAtExit sync; const Ws W = d.prepare(n, s);
+  grow_buf(d.io, up + down); uint32_t *in = d.io.get(), *out = in + up;
+  SyncAtExit sync; const Ws W = d.prepare(n, s);
   HIP_CHECK(hipMemcpyAsync(in, pu, 4 * up, hipMemcpyHostToDevice, s));
   d.body(n, in, in + 8 * n, (const uint8_t *)(in + 24 * n), homestead, W, out, pubs != nullptr, s);
   HIP_CHECK(hipMemcpyAsync(back, out, 4 * down, hipMemcpyDeviceToHost, s)); HIP_CHECK(hipStreamSynchronize(s));
@@ -240,8 +235,8 @@ void probe_secp_lincomb(const uint8_t *u1, const uint8_t *u2, const uint8_t *px,
   const size_t okw = (n + 3) / 4, up = 32 * n, down = SP_HEAD + okw + 5 * n + 16 * n;
   d.pinned(4 * (up + down)); uint8_t *const back = d.pin + 4 * up;
   memcpy(d.pin, u1, 32 * n); memcpy(d.pin + 32 * n, u2, 32 * n); memcpy(d.pin + 64 * n, px, 32 * n); memcpy(d.pin + 96 * n, py, 32 * n);
-  Senders::grow(d.io, up + down); uint32_t *in = d.io.get(), *out = in + up;
-  Senders::SyncAtExit sync; const Ws W = d.prepare(n, s);
+  grow_buf(d.io, up + down); uint32_t *in = d.io.get(), *out = in + up;
+  SyncAtExit sync; const Ws W = d.prepare(n, s);
   HIP_CHECK(hipMemcpyAsync(in, d.pin, 4 * up, hipMemcpyHostToDevice, s));
   hipLaunchKernelGGL(k_secp_load_lincomb, dim3(cdiv(n, SP_THREADS)), dim3(SP_THREADS), 0, s, (const uint32_t *)in, (uint32_t)n, W);
   d.tail(n, W, out, true, s);

@@ -265,13 +265,10 @@ __global__ void __launch_bounds__(MATCH_THREADS) k_tree_match_roots_window(const
 struct CommitmentTree::Impl {
   std::mutex mu; uint32_t depth = 0, cap_log = 0; uint64_t n = 0; DevBuf<uint8_t> nodes, empty, out, first /* k_tree_find's word */; std::vector<uint8_t> empty_host;
   uint64_t launches = 0, state_launches = 0; DevBuf<uint8_t> q_in, q_out;   // past states: the sizes or indices of a call, and its answer (kept and grown)
-  static void grow(DevBuf<uint8_t> &b, size_t bytes) { if (b.size() < bytes) b = DevBuf<uint8_t>(std::max(bytes, 2 * b.size())); }
-  // the main stream is synchronised when a past-state entry returns or throws: nothing still reads the caller's arrays or writes the host vector then
-  struct SyncAtExit { ~SyncAtExit() { (void)hipStreamSynchronize(gpu().stream); } };
   // [root | index | q paths] of state m >= 1 in one download: the indices from the host or (from_find, q = 1) from k_tree_find's word
   void fetch_at(uint64_t m, const uint64_t *indices, size_t q, bool from_find, std::vector<uint8_t> &host) {
-    hipStream_t s = gpu().stream; const size_t bytes = 64 + 32 * q * depth; grow(q_out, bytes);
-    if (!from_find && q) { grow(q_in, 8 * q); HIP_CHECK(hipMemcpyAsync(q_in.get(), indices, 8 * q, hipMemcpyHostToDevice, s)); }
+    hipStream_t s = gpu().stream; const size_t bytes = 64 + 32 * q * depth; grow_buf(q_out, bytes);
+    if (!from_find && q) { grow_buf(q_in, 8 * q); HIP_CHECK(hipMemcpyAsync(q_in.get(), indices, 8 * q, hipMemcpyHostToDevice, s)); }
     const unsigned nb = (unsigned)std::min<uint64_t>(std::max<uint64_t>(cdiv(q * depth, 256), 1), 256);
     hipLaunchKernelGGL(k_tree_paths_at, dim3(nb), dim3(256), 0, s, geom(), m, from_find ? nullptr : (const unsigned long long *)q_in.get(),
                        from_find ? (const unsigned long long *)first.get() : nullptr, (uint64_t)q, q_out.get()); state_launches++;
@@ -373,7 +370,7 @@ bool CommitmentTree::roots_at(const uint64_t *sizes, size_t q, uint8_t *out) {
   for (size_t i = 0; i < q; i++) if (sizes[i] > d.n) return false;
   if (!q) return true;
   LaneScope lane(0); std::lock_guard<std::mutex> gl(g_gpu_mutex); hipStream_t s = gpu().stream;
-  d.grow(d.q_in, 8 * q); d.grow(d.q_out, 32 * q); std::vector<uint8_t> h(32 * q); Impl::SyncAtExit sync;   // (the vector outlives the synchronise)
+  grow_buf(d.q_in, 8 * q); grow_buf(d.q_out, 32 * q); std::vector<uint8_t> h(32 * q); SyncAtExit sync;   // (the vector outlives the synchronise)
   HIP_CHECK(hipMemcpyAsync(d.q_in.get(), sizes, 8 * q, hipMemcpyHostToDevice, s));
   hipLaunchKernelGGL(k_tree_roots_at, dim3((unsigned)cdiv(q, 64)), dim3(64), 0, s, d.geom(), (const unsigned long long *)d.q_in.get(), (uint64_t)q, d.q_out.get()); d.state_launches++;
   HIP_CHECK(hipGetLastError()); d.q_out.download(h.data(), h.size());
@@ -389,7 +386,7 @@ bool CommitmentTree::match_roots(const uint64_t *sizes, size_t m, const uint8_t 
   if (!m) { for (size_t i = 0; i < q; i++) match_out[i] = -1; return true; }
   LaneScope lane(0); std::lock_guard<std::mutex> gl(g_gpu_mutex); hipStream_t s = gpu().stream;
   std::vector<uint8_t> up(8 * m + 32 * q); memcpy(up.data(), sizes, 8 * m); memcpy(up.data() + 8 * m, rts, 32 * q);
-  d.grow(d.q_in, up.size()); d.grow(d.q_out, 32 * m + 4 * q); std::vector<int32_t> h(q); Impl::SyncAtExit sync;   // (the vectors outlive the synchronise)
+  grow_buf(d.q_in, up.size()); grow_buf(d.q_out, 32 * m + 4 * q); std::vector<int32_t> h(q); SyncAtExit sync;   // (the vectors outlive the synchronise)
   HIP_CHECK(hipMemcpyAsync(d.q_in.get(), up.data(), up.size(), hipMemcpyHostToDevice, s));
   hipLaunchKernelGGL(k_tree_roots_at, dim3((unsigned)cdiv(m, 64)), dim3(64), 0, s, d.geom(), (const unsigned long long *)d.q_in.get(), (uint64_t)m, d.q_out.get()); d.state_launches++;
   hipLaunchKernelGGL(k_tree_match_roots, dim3((unsigned)cdiv(q, MATCH_THREADS)), dim3(MATCH_THREADS), 0, s, (const uint32_t *)d.q_out.get(), (uint32_t)m,
@@ -410,7 +407,7 @@ bool CommitmentTree::match_roots_window(const uint64_t *sizes, size_t m, const u
   LaneScope lane(0); std::lock_guard<std::mutex> gl(g_gpu_mutex); hipStream_t s = gpu().stream;
   const size_t at_rts = 8 * m, at_lo = at_rts + 32 * q, at_hi = at_lo + 4 * q;                   // (8 m and 32 q keep the words aligned)
   std::vector<uint8_t> up(at_hi + 4 * q); memcpy(up.data(), sizes, 8 * m); memcpy(up.data() + at_rts, rts, 32 * q); memcpy(up.data() + at_lo, lo, 4 * q); memcpy(up.data() + at_hi, hi, 4 * q);
-  d.grow(d.q_in, up.size()); d.grow(d.q_out, 32 * m + 4 * q); std::vector<int32_t> h(q); Impl::SyncAtExit sync;   // (the vectors outlive the synchronise)
+  grow_buf(d.q_in, up.size()); grow_buf(d.q_out, 32 * m + 4 * q); std::vector<int32_t> h(q); SyncAtExit sync;   // (the vectors outlive the synchronise)
   HIP_CHECK(hipMemcpyAsync(d.q_in.get(), up.data(), up.size(), hipMemcpyHostToDevice, s));
   hipLaunchKernelGGL(k_tree_roots_at, dim3((unsigned)cdiv(m, 64)), dim3(64), 0, s, d.geom(), (const unsigned long long *)d.q_in.get(), (uint64_t)m, d.q_out.get()); d.state_launches++;
   hipLaunchKernelGGL(k_tree_match_roots_window, dim3((unsigned)cdiv(q, MATCH_THREADS)), dim3(MATCH_THREADS), 0, s, (const uint32_t *)d.q_out.get(), (const uint32_t *)(d.q_in.get() + at_rts),
@@ -425,14 +422,14 @@ bool CommitmentTree::paths_at(uint64_t size, const uint64_t *indices, size_t q, 
   for (size_t i = 0; i < q; i++) if (indices[i] >= size) return false;
   if (!size) { if (root) memcpy(root, &d.empty_host[32 * d.depth], 32); return true; }          // (q = 0 here: no index lies below 0)
   if (!q && !root) return true;
-  LaneScope lane(0); std::lock_guard<std::mutex> gl(g_gpu_mutex); std::vector<uint8_t> h; Impl::SyncAtExit sync; d.fetch_at(size, indices, q, false, h);
+  LaneScope lane(0); std::lock_guard<std::mutex> gl(g_gpu_mutex); std::vector<uint8_t> h; SyncAtExit sync; d.fetch_at(size, indices, q, false, h);
   if (q) memcpy(siblings, h.data() + 64, 32 * q * d.depth);
   if (root) memcpy(root, h.data(), 32);
   return true;
 }
 bool CommitmentTree::find_at(uint64_t size, const uint8_t leaf[32], uint64_t &index) {
   Impl &d = *impl; std::lock_guard<std::mutex> lk(d.mu); if (size > d.n || !leaf || !size) return false;
-  LaneScope lane(0); std::lock_guard<std::mutex> gl(g_gpu_mutex); uint64_t got = 0; Impl::SyncAtExit sync; d.find_async(leaf, size); d.state_launches++; HIP_CHECK(hipGetLastError());
+  LaneScope lane(0); std::lock_guard<std::mutex> gl(g_gpu_mutex); uint64_t got = 0; SyncAtExit sync; d.find_async(leaf, size); d.state_launches++; HIP_CHECK(hipGetLastError());
   d.first.download((uint8_t *)&got, 8); if (got >= size) return false;
   index = got; return true;
 }
@@ -440,7 +437,7 @@ bool CommitmentTree::snapshot_at(uint64_t size, const uint8_t leaf[32], Snapshot
   Impl &d = *impl; std::lock_guard<std::mutex> lk(d.mu); out.size = size; out.path.assign(32 * d.depth, 0); out.index_bits.assign(d.depth, false); out.index = 0;
   memcpy(out.root, &d.empty_host[32 * d.depth], 32);
   if (size > d.n || !size || !leaf) return false;                                                 // (a size the tree does not hold: the empty root, and false)
-  LaneScope lane(0); std::lock_guard<std::mutex> gl(g_gpu_mutex); std::vector<uint8_t> h; Impl::SyncAtExit sync;
+  LaneScope lane(0); std::lock_guard<std::mutex> gl(g_gpu_mutex); std::vector<uint8_t> h; SyncAtExit sync;
   d.find_async(leaf, size); d.state_launches++; d.fetch_at(size, nullptr, 1, true, h);            // find, edge walk and gather, one download
   memcpy(out.root, h.data(), 32);
   uint64_t got; memcpy(&got, h.data() + 32, 8); if (got >= size) return false;

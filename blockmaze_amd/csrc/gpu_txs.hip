@@ -248,11 +248,8 @@ __global__ void __launch_bounds__(TX_THREADS) k_tx_finish(uint32_t n, const uint
 
 // ---- the host side ------------------------------------------------------------------------------------------------------------------------------------------------
 namespace {
-struct Txs {                                         // one a process, every member under the device mutex
-  DevBuf<uint32_t> io; uint8_t *pin = nullptr; size_t pin_bytes = 0;
-  struct SyncAtExit { ~SyncAtExit() { (void)hipStreamSynchronize(gpu().stream); } };   // nothing reads pinned or caller memory once an entry has returned or thrown
-  void pinned(size_t bytes) { if (pin_bytes >= bytes) return; if (pin) { (void)hipHostFree(pin); pin = nullptr; pin_bytes = 0; }
-    HIP_CHECK(hipHostMalloc((void **)&pin, 2 * bytes)); pin_bytes = 2 * bytes; }
+struct Txs : PinnedStage {                           // one a process, every member under the device mutex
+  DevBuf<uint32_t> io;
   void grow(size_t words) { if (io.size() >= words) return; const size_t want = std::max(words, 2 * io.size()); io = DevBuf<uint32_t>(); io = DevBuf<uint32_t>(want); }   // (a failed growth leaves no workspace)
 };
 Txs &txs_state() { static Txs *t = new Txs; return *t; }   // (never destroyed: the runtime may be gone when statics are)
@@ -281,7 +278,7 @@ size_t tx_sender_inputs(const uint8_t *txs, const uint64_t *off, size_t n, int s
   const uint8_t *dtx = (const uint8_t *)p; const uint64_t *doff = (const uint64_t *)((const uint8_t *)p + total8);
   uint32_t *D = p + w_up, *hash = D + w_D, *rs = hash + 8 * n, *v = rs + 16 * n, *rec = v + okw, *dn = rec + w_rec;
   uint32_t *d_txhash = dn, *d_sighash = dn + 8 * n, *d_froms = dn + 16 * n; uint8_t *d_sigs = (uint8_t *)(dn + 21 * n), *d_status = d_sigs + 4 * ((65 * n + 3) / 4), *d_code = d_status + 4 * okw; uint32_t *d_head = dn + down_words - 4;
-  Txs::SyncAtExit sync;
+  SyncAtExit sync;
   HIP_CHECK(hipMemcpyAsync(p, d.pin, up, hipMemcpyHostToDevice, s));
   const dim3 block(TX_THREADS), grid(cdiv(n, TX_THREADS)), grid2(cdiv(2 * n, TX_THREADS));
   hipLaunchKernelGGL(k_tx_walk, grid, block, 0, s, dtx, doff, (uint32_t)n, signer, chain_id, D, (uint8_t *)rs, (uint8_t *)v, want_senders ? (uint8_t *)nullptr : d_sigs);
@@ -311,7 +308,7 @@ void probe_keccak256(const uint8_t *msgs, const uint64_t *off, size_t n, uint8_t
   LaneScope lane(0); hipStream_t s = gpu().stream; Txs &d = txs_state(); uint8_t *back = nullptr;
   const size_t up = stage(d, msgs, off, n, 32 * n, &back), total8 = up - 8 * (n + 1), words = up / 4 + 8 * n + 2;
   d.grow(words); uint32_t *p = d.io.get(); if (!p) throw GpuError("txs: no workspace");
-  Txs::SyncAtExit sync;
+  SyncAtExit sync;
   HIP_CHECK(hipMemcpyAsync(p, d.pin, up, hipMemcpyHostToDevice, s));
   hipLaunchKernelGGL(k_tx_keccak, dim3(cdiv(n, TX_THREADS)), dim3(TX_THREADS), 0, s, (const uint8_t *)p, (const uint64_t *)((const uint8_t *)p + total8), (uint32_t)n, p + up / 4);
   HIP_CHECK(hipGetLastError());
