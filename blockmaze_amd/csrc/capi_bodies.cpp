@@ -1,0 +1,125 @@
+// extern "C" surface of the records from the block bodies' bytes and of the chain call on them (include/zk_bodies.h, include/zkgpu.h "Records from the block
+// bodies' bytes"): the arguments are checked here, before anything is queued; the device work is gpu_txs.hip's, the decision on the records is
+// verifyChainAccounts'.  Every C++ exception ends at this boundary.
+#include <cstdio>
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <vector>
+#include "../../include/zkgpu.h"
+#include "../../include/zk_bodies.h"
+#include "gpu.hpp"
+
+extern std::mutex g_gpu_mutex;
+extern void zkgpu_set_error(const std::string &s);
+namespace zk {
+size_t tx_records(const uint8_t *txs, const uint64_t *off, size_t n, int signer, uint64_t chain_id, uint8_t *recs, uint8_t *rec_froms, int32_t *rec_of, uint8_t *txhash, uint8_t *froms,
+                  uint8_t *code, uint8_t *status, size_t *first_bad, const int *borders, size_t n_borders, int *rec_borders);
+void tx_records_gather_bytewise(bool on);
+}
+using namespace zk;
+
+namespace {
+const char *const NO_DEVICE = "no HIP device visible; libzkgpu has no CPU fallback";
+struct BodyOut { zk_block_record *recs; uint8_t *rec_froms; int32_t *rec_of; uint8_t *txhash, *froms, *code, *status; };
+// every output as a failure leaves it: nothing is written through a null pointer or for a negative count
+void bodies_zero(int n, const BodyOut &o) {
+  if (n <= 0) return;
+  if (o.recs) memset(o.recs, 0, sizeof(zk_block_record) * (size_t)n);
+  if (o.rec_froms) memset(o.rec_froms, 0, 20 * (size_t)n);
+  if (o.rec_of) memset(o.rec_of, 0, 4 * (size_t)n);
+  if (o.txhash) memset(o.txhash, 0, 32 * (size_t)n);
+  if (o.froms) memset(o.froms, 0, 20 * (size_t)n);
+  if (o.code) memset(o.code, 0, (size_t)n);
+  if (o.status) memset(o.status, 0, (size_t)n);
+}
+// zkTxSenders' refusals (capi_txs.cpp: txs_args_ok), and the three arrays of the records
+bool bodies_args_ok(const uint8_t *txs, const uint64_t *off, int n, int signer, uint64_t chain_id, const BodyOut &o) {
+  if (n < 0) { zkgpu_set_error("bodies: a negative count"); return false; }
+  if (n && (!txs || !off || !o.froms || !o.code || !o.status || !o.recs || !o.rec_froms || !o.rec_of)) { zkgpu_set_error("bodies: a null pointer"); return false; }
+  if (signer != ZK_SIGNER_FRONTIER && signer != ZK_SIGNER_HOMESTEAD && signer != ZK_SIGNER_EIP155) { zkgpu_set_error("bodies: an unknown signer"); return false; }
+  if (chain_id >> 62) { zkgpu_set_error("bodies: a chain id of 2^62 or more"); return false; }
+  for (int i = 0; i < n; i++) if (off[i + 1] < off[i]) { zkgpu_set_error("bodies: offsets decrease"); return false; }
+  return true;
+}
+// the device part under the device mutex: m, or ZKGPU_ERR_NO_DEVICE / ZKGPU_ERR_RUNTIME with every output zeroed
+int bodies_run(const uint8_t *txs, const uint64_t *off, int n, int signer, uint64_t chain_id, const BodyOut &o, size_t *first_bad, const int *borders, size_t n_borders, int *rec_borders) {
+  int rc;
+  try {
+    if (!gpu_available()) { zkgpu_set_error(NO_DEVICE); rc = ZKGPU_ERR_NO_DEVICE; }
+    else { std::lock_guard<std::mutex> lk(g_gpu_mutex);
+      rc = (int)tx_records(txs, off, (size_t)n, signer, chain_id, (uint8_t *)o.recs, o.rec_froms, o.rec_of, o.txhash, o.froms, o.code, o.status, first_bad, borders, n_borders, rec_borders); }
+  }
+  catch (const std::exception &e) { zkgpu_set_error(e.what()); rc = ZKGPU_ERR_RUNTIME; }
+  catch (...) { zkgpu_set_error("unknown error"); rc = ZKGPU_ERR_RUNTIME; }
+  if (rc < 0) bodies_zero(n, o);                                                                    // a step failed midway: nothing half-written stays
+  return rc;
+}
+}  // namespace
+
+extern "C" {
+int zkgpu_tx_records(const uint8_t *txs, const uint64_t *off, int n, int signer, uint64_t chain_id, zk_block_record *recs, uint8_t *rec_froms, int32_t *rec_of, uint8_t *txhash,
+                     uint8_t *froms, uint8_t *code, uint8_t *status) {
+  const BodyOut o = {recs, rec_froms, rec_of, txhash, froms, code, status};
+  if (!bodies_args_ok(txs, off, n, signer, chain_id, o)) { bodies_zero(n, o); return ZKGPU_ERR_ARG; }   // (before the device is asked for)
+  if (n == 0) return 0;
+  return bodies_run(txs, off, n, signer, chain_id, o, nullptr, nullptr, 0, nullptr);
+}
+int zkTxRecords(const uint8_t *txs, const uint64_t *off, int n, int signer, uint64_t chain_id, zk_block_record *recs, uint8_t (*rec_froms)[20], int32_t *rec_of, uint8_t (*txhash)[32],
+                uint8_t (*froms)[20], uint8_t *code, uint8_t *status) {
+  const int rc = zkgpu_tx_records(txs, off, n, signer, chain_id, recs, (uint8_t *)rec_froms, rec_of, (uint8_t *)txhash, (uint8_t *)froms, code, status);
+  if (rc < 0) { fprintf(stderr, "libzkgpu: zkTxRecords: %s\n", zkgpu_last_error()); return -1; }
+  return rc;
+}
+int zkgpu_test_bodies_gather(int bytewise) { std::lock_guard<std::mutex> lk(g_gpu_mutex); tx_records_gather_bytewise(bytewise != 0); return ZKGPU_OK; }
+
+int verifyChainBodies(zk_proof_cache *cache, const uint8_t *txs, const uint64_t *off, int n, const int *block_first, int n_blocks, int signer, uint64_t chain_id, zk_accts *accts,
+                      zk_tree *tree, const long long *prior_anchors, int n_prior, int window, zk_snset *set, zk_block_record *recs, uint8_t (*rec_froms)[20], int32_t *rec_of,
+                      uint8_t (*txhash)[32], uint8_t (*froms)[20], uint8_t *code, uint8_t *status, unsigned char *ok, int32_t *anchor_of, long long *accts_sizes, long long *set_sizes,
+                      long long *tree_sizes, int *n_recs) {
+  const BodyOut o = {recs, (uint8_t *)rec_froms, rec_of, (uint8_t *)txhash, (uint8_t *)froms, code, status};
+  // every output zeroed; anchor_of: -1, "no anchor", as verifyChainAccounts leaves it.  The sizes arrays are not written: verifyChainAccounts may have reported the
+  // sizes after an impossible rewind in their last entries (zk_accounts_chain.h).
+  auto fail = [&](const std::string &why) {
+    zkgpu_set_error(why); fprintf(stderr, "libzkgpu: verifyChainBodies: %s\n", why.c_str());
+    bodies_zero(n, o);
+    for (int i = 0; i < n; i++) { if (ok) ok[i] = 0; if (anchor_of) anchor_of[i] = -1; }
+    if (n_recs) *n_recs = 0;
+    return -1; };
+  try {
+    // 0. the arguments of both parts — verifyChainAccounts looks at its own again — before anything is queued or written
+    if (!bodies_args_ok(txs, off, n, signer, chain_id, o)) return fail(zkgpu_last_error());
+    if (n_blocks < 0 || (n && !ok) || !n_recs) return fail("a negative count or a null pointer");
+    if (!tree) return fail("no tree");
+    if (!accts) return fail("no account table");
+    if (!block_first || block_first[0] != 0 || block_first[n_blocks] != n) return fail("block_first does not run from 0 to n");
+    for (int b = 0; b < n_blocks; b++) if (block_first[b] > block_first[b + 1]) return fail("block_first decreases at block " + std::to_string(b));
+    if (n_prior < 0 || (n_prior && !prior_anchors)) return fail("a negative number of prior anchors or a null pointer");
+    if (window < 0) return fail("a negative window");
+    if (!gpu_available()) return fail(NO_DEVICE);
+    uint64_t tree_before = 0; if (zkgpu_tree_size((zkgpu_tree *)tree, &tree_before) != ZKGPU_OK) return fail(zkgpu_last_error());
+    for (int a = 0; a < n_prior; a++) if (prior_anchors[a] < 0 || (uint64_t)prior_anchors[a] > tree_before) return fail("prior anchor " + std::to_string(a) + " is negative or above the tree's size");
+    // 1. zkTxRecords on all n transactions; the records before each block border from the prefix values the device left
+    std::vector<int> rec_first((size_t)n_blocks + 1, 0); size_t first_bad = 0; int m = 0;
+    if (n) { m = bodies_run(txs, off, n, signer, chain_id, o, &first_bad, block_first, (size_t)n_blocks + 1, rec_first.data()); if (m < 0) return fail(zkgpu_last_error()); }
+    // 2. B0: the first block that holds a transaction with status != ZK_TX_OK
+    int B0 = n_blocks;
+    if (n && first_bad < (size_t)n) { B0 = 0; while (B0 < n_blocks && (size_t)block_first[B0 + 1] <= first_bad) B0++; }
+    // 3. verifyChainAccounts on the records of blocks [0, B0); a refusal there has left the three states alone
+    const int n0 = rec_first[B0];
+    const int k = verifyChainAccounts(cache, recs, (const uint8_t (*)[20])rec_froms, n0, rec_first.data(), B0, accts, tree, prior_anchors, n_prior, window, set, ok, anchor_of, accts_sizes, set_sizes, tree_sizes);
+    if (k < 0) return fail(zkgpu_last_error());
+    // 4. from B0 on nothing is decided, and the sizes are the ones the call leaves
+    for (int j = n0; j < m; j++) { ok[j] = 0; if (anchor_of) anchor_of[j] = -1; }
+    if (B0 < n_blocks) {
+      long long a_now = B0 && accts_sizes ? accts_sizes[B0 - 1] : zkAcctsSize(accts), s_now = B0 && set_sizes ? set_sizes[B0 - 1] : (set ? zkSnSetSize(set) : 0), t_now = B0 && tree_sizes ? tree_sizes[B0 - 1] : 0;
+      if (!(B0 && tree_sizes)) { uint64_t t = 0; if (zkgpu_tree_size((zkgpu_tree *)tree, &t) != ZKGPU_OK) t = tree_before; t_now = (long long)t; }
+      for (int b = B0; b < n_blocks; b++) { if (accts_sizes) accts_sizes[b] = a_now; if (set && set_sizes) set_sizes[b] = s_now; if (tree_sizes) tree_sizes[b] = t_now; }
+    }
+    *n_recs = m;
+    return k;
+  }
+  catch (const std::exception &e) { return fail(e.what()); }
+  catch (...) { return fail("unknown error"); }
+}
+}  // extern "C"

@@ -7,6 +7,12 @@
 //                 of the input with at most one byte substituted, a suffix in registers)
 //   (the recovery's six launches, gpu_senders.hip, on what the two left on the device: zkTxSenders only)
 //   k_tx_finish   the walk's status merged with the recovery's ok; a deposit's sender is its ZKAdrress; refused lanes zero
+// and, for zkTxRecords (include/zk_bodies.h), the same walk instantiated with a second descriptor (the positions of the ZK fields, X and Y padded, a
+// deposit on HomesteadSigner's road), the same hashes and the same recovery, then
+//   k_body_finish   k_tx_finish with the deposit's key rule (core/state_processor.go:141-146) and the count of records of each workgroup
+//   k_body_scan     the exclusive scan of those counts, one workgroup
+//   k_body_scatter  rec_of, the n + 1 prefix values, the transaction of each record, rec_froms
+//   k_body_gather   a wave a record: the 180 words of a zk_block_record from the transaction's bytes
 // Rules every kernel keeps: no lane waits for another lane; every loop is bounded by a constant or by the transaction's own length; every
 // offset taken from the input is checked against the end of its list — and so against the transaction's end — before the byte there is read; the Keccak state is
 // indexed by compile-time constants only; no kernel uses scratch.
@@ -22,14 +28,18 @@ void recover_senders_queue(const uint32_t *hash, const uint32_t *rs, const uint8
 void senders_keep_head(const uint32_t *head);
 
 constexpr int TX_THREADS = 128;
-enum { TX_OK = 0, TX_MALFORMED = 1, TX_CHAIN_ID = 2, TX_SIG = 3 };
+enum { TX_OK = 0, TX_MALFORMED = 1, TX_CHAIN_ID = 2, TX_SIG = 3, TX_DEPOSIT_KEY = 4 };
 enum { SIGNER_FRONTIER = 0, SIGNER_HOMESTEAD = 1, SIGNER_EIP155 = 2 };
 constexpr uint32_t TX_DEPOSIT = 3;                    // transaction.go:43
 // the descriptor of a lane, in words; word k of lane i lies at D[k * n + i]
 constexpr int TD_META = 0 /* status | code << 8 | nine-field hash << 16 */, TD_A = 1, TD_B = 2, TD_C0 = 3 /* 0xFFFFFFFF: none */, TD_ZK = 4, TD_WORDS = 9;
 // txdata's 26 fields (transaction.go:64-96), three bits a field
 enum { FK_U8, FK_U64, FK_BIG, FK_ADDR_NIL, FK_BYTES, FK_HASH, FK_ADDR, FK_U64S };
-constexpr int TX_FIELDS = 26, F_RECIPIENT = 4, F_PAYLOAD = 6, F_ZKADDR = 11, F_V = 23, F_R = 24, F_S = 25;
+constexpr int TX_FIELDS = 26, F_RECIPIENT = 4, F_PAYLOAD = 6, F_ZKVALUE = 7, F_ZKSN = 8, F_ZKSNS = 9, F_ZKADDR = 11, F_ZKCMT = 12, F_ZKCMTS = 13, F_ZKPROOF = 14, F_RTCMT = 15, F_X = 18, F_Y = 19,
+              F_V = 23, F_R = 24, F_S = 25;
+// the second descriptor of a lane (zkTxRecords only), word k of lane i at E[k * n + i]: ZKValue, the content positions of the five hashes, ZKProof's position and size,
+// "X and Y have at most 32 bytes"
+constexpr int TE_VAL_LO = 0, TE_VAL_HI = 1, TE_SN = 2, TE_SNS = 3, TE_CMT = 4, TE_CMTS = 5, TE_RT = 6, TE_PROOF = 7, TE_PROOF_SIZE = 8, TE_XY_OK = 9, TE_WORDS = 10;
 constexpr uint64_t fk_pack(const int *k, int from, int to) { uint64_t v = 0; for (int i = from; i < to; i++) v |= (uint64_t)k[i] << (3 * (i - from)); return v; }
 constexpr int FKINDS[TX_FIELDS] = {FK_U8, FK_U64, FK_BIG, FK_U64, FK_ADDR_NIL, FK_BIG, FK_BYTES, FK_U64, FK_HASH, FK_HASH, FK_U64, FK_ADDR, FK_HASH, FK_HASH, FK_BYTES, FK_HASH,
                                     FK_U64S, FK_BYTES, FK_BIG, FK_BIG, FK_BIG, FK_BIG, FK_BIG, FK_BIG, FK_BIG, FK_BIG};
@@ -74,9 +84,15 @@ __device__ __forceinline__ void tx_put32(uint8_t *__restrict__ dst, const uint8_
 #pragma unroll 4
   for (uint32_t k = 0; k < 32; k++) dst[k] = (want && size <= 32u && k >= pad) ? t[beg + (k - pad)] : (uint8_t)0;
 }
+// BODIES (zkTxRecords): E, xy and first_bad are written as well, and a deposit takes HomesteadSigner's road; without it they are never touched and the kernel is the
+// one zkTxSigningInputs and zkTxSenders have always run.
+template <bool BODIES>
 __global__ void __launch_bounds__(TX_THREADS) k_tx_walk(const uint8_t *__restrict__ txs, const uint64_t *__restrict__ off, uint32_t n, int signer, uint64_t chain_id, uint32_t *__restrict__ D,
-                                                         uint8_t *__restrict__ rs, uint8_t *__restrict__ vout, uint8_t *__restrict__ sigs65) {
+                                                         uint8_t *__restrict__ rs, uint8_t *__restrict__ vout, uint8_t *__restrict__ sigs65, uint32_t *__restrict__ E, uint8_t *__restrict__ xy,
+                                                         uint32_t *__restrict__ first_bad) {
   const uint32_t i = blockIdx.x * TX_THREADS + threadIdx.x; if (i >= n) return;
+  uint32_t valbeg = 0, valsize = 0, sn = 0, sns = 0, cmt = 0, cmts = 0, rt = 0, pbeg = 0, psize = 0, xbeg = 0, xsize = 0, ybeg = 0, ysize = 0;   // (dead without BODIES)
+  if constexpr (BODIES) { if (i == 0) first_bad[0] = n; }                                          // k_body_finish's atomicMin starts from "none"
   const uint64_t base = off[0], o0 = off[i] - base, len64 = off[i + 1] - off[i]; const uint8_t *t = txs + o0;   // (the host has checked that off does not decrease)
   bool bad = len64 == 0 || len64 > 0xFFFFFFFFull; const uint32_t len = (uint32_t)len64;
   uint32_t code = 0, a = 0, b = 0, c0 = 0xFFFFFFFFu, zk = 0, vbeg = 0, vsize = 0, rbeg = 0, rsize = 0, sbeg = 0, ssize = 0, pos = 0, lim = 0;
@@ -109,6 +125,17 @@ __global__ void __launch_bounds__(TX_THREADS) k_tx_walk(const uint8_t *__restric
     if (f == F_V) { vbeg = h.beg; vsize = h.size; }
     if (f == F_R) { rbeg = h.beg; rsize = h.size; }
     if (f == F_S) { sbeg = h.beg; ssize = h.size; }
+    if constexpr (BODIES) {
+      if (f == F_ZKVALUE) { valbeg = h.beg; valsize = h.size; }
+      if (f == F_ZKSN) sn = h.beg;
+      if (f == F_ZKSNS) sns = h.beg;
+      if (f == F_ZKCMT) cmt = h.beg;
+      if (f == F_ZKCMTS) cmts = h.beg;
+      if (f == F_ZKPROOF) { pbeg = h.beg; psize = h.size; }
+      if (f == F_RTCMT) rt = h.beg;
+      if (f == F_X) { xbeg = h.beg; xsize = h.size; }
+      if (f == F_Y) { ybeg = h.beg; ysize = h.size; }
+    }
   }
   if (!bad && pos != lim) bad = true;                                                               // :449, :778: too many elements
   uint32_t status = TX_MALFORMED, nine = 0, vbyte = 0; bool put_v = false, put_r = false, put_s = false;
@@ -126,6 +153,15 @@ __global__ void __launch_bounds__(TX_THREADS) k_tx_walk(const uint8_t *__restric
     vbyte = (uint32_t)((vs - 27) & 0xFFu);                                                          // :250
     if (code == TX_DEPOSIT) { status = TX_OK; put_r = rsize <= 32; put_s = ssize <= 32; put_v = vfits; }   // :72-76: V, R, S never looked at; written where they fit
     else { status = mismatch ? TX_CHAIN_ID : (!vfits || rsize > 32 || ssize > 32) ? TX_SIG : TX_OK; put_r = put_s = put_v = status == TX_OK; }   // :155-157, :247, :255-258
+    if constexpr (BODIES) {
+      if (code == TX_DEPOSIT) {                                                                     // state_processor.go:141: ExtractPKBAddress(HomesteadSigner{}, tx), whatever the block's signer
+        nine = 0;                                                                                   // transaction_signing.go:206-208 with :231-240: HomesteadSigner hashes six fields, always
+        const bool v_ok = vsize <= 1 && (v == 27 || v == 28);                                       // :96-113 -> recoverPlain :247 BitLen() > 8, :250 V - 27, crypto.go:209 v == 0 || v == 1; no chain id
+        vbyte = (uint32_t)((v - 27) & 0xFFu);
+        status = (v_ok && rsize <= 32 && ssize <= 32) ? TX_OK : TX_DEPOSIT_KEY;                     // :255-258: R and S go into 32-byte fields
+        put_r = put_s = put_v = status == TX_OK;
+      }
+    }
   }
   const size_t nn = n;
   D[TD_META * nn + i] = status | (bad ? 0u : code << 8) | (nine << 16); D[TD_A * nn + i] = a; D[TD_B * nn + i] = b; D[TD_C0 * nn + i] = c0;
@@ -135,6 +171,16 @@ __global__ void __launch_bounds__(TX_THREADS) k_tx_walk(const uint8_t *__restric
     D[(TD_ZK + k) * nn + i] = w; }
   tx_put32(rs + 64 * (size_t)i, t, rbeg, rsize, put_r); tx_put32(rs + 64 * (size_t)i + 32, t, sbeg, ssize, put_s); vout[i] = put_v ? (uint8_t)vbyte : (uint8_t)0;
   if (sigs65) { uint8_t *q = sigs65 + 65 * (size_t)i; tx_put32(q, t, rbeg, rsize, put_r); tx_put32(q + 32, t, sbeg, ssize, put_s); q[64] = put_v ? (uint8_t)vbyte : (uint8_t)0; }
+  if constexpr (BODIES) {
+    uint64_t val = 0;                                                                               // ZKValue: at most 8 bytes (the walk has refused more)
+#pragma unroll
+    for (uint32_t k = 0; k < 8; k++) if (!bad && k < valsize && valsize <= 8) val = (val << 8) | t[valbeg + k];
+    const bool dep = !bad && code == TX_DEPOSIT && status == TX_OK, xy_ok = xsize <= 32 && ysize <= 32;   // crypto.go:136-141: elliptic.Marshal cannot hold more than 32 bytes a coordinate
+    const uint32_t e[TE_WORDS] = {(uint32_t)val, (uint32_t)(val >> 32), sn, sns, cmt, cmts, rt, pbeg, psize, xy_ok ? 1u : 0u};
+#pragma unroll
+    for (int k = 0; k < TE_WORDS; k++) E[k * nn + i] = bad ? 0u : e[k];
+    tx_put32(xy + 64 * (size_t)i, t, xbeg, xsize, dep && xy_ok); tx_put32(xy + 64 * (size_t)i + 32, t, ybeg, ysize, dep && xy_ok);   // pad32(X) || pad32(Y)
+  }
 }
 
 // ---- the sponge ---------------------------------------------------------------------------------------------------------------------------------------------------
@@ -246,6 +292,138 @@ __global__ void __launch_bounds__(TX_THREADS) k_tx_finish(uint32_t n, const uint
   status_out[i] = (uint8_t)status; code_out[i] = (uint8_t)code;
 }
 
+// ---- records from the bodies' bytes (include/zk_bodies.h) ------------------------------------------------------------------------------------------
+constexpr int BODY_SCAN_THREADS = 256, BODY_GATHER_THREADS = 256, REC_WORDS = 180;                 // (a scan tile covers 256 x 128 = 32,768 transactions)
+constexpr uint32_t KIND_MINT = 0, KIND_SEND = 1, KIND_DEPOSIT = 2, KIND_REDEEM = 3;                // zk_batch.h
+enum { BH_FIRST_BAD = 0, BH_M = 1, BH_WORDS = 4 };
+// txdata.Code (transaction.go:40-46) -> ZK_KIND_* + 1, 0 where ApplyTransaction has no ZK branch (state_processor.go:108-164: codes 0 and 4, and every code above 5)
+__device__ __forceinline__ uint32_t body_kind1(uint32_t code) { return code == 1 ? KIND_MINT + 1 : code == 2 ? KIND_SEND + 1 : code == 3 ? KIND_DEPOSIT + 1 : code == 5 ? KIND_REDEEM + 1 : 0u; }
+// a > floor(N / 2)
+__device__ __forceinline__ bool above_half_n(const secp::U256 &a) { uint64_t br = 0;
+#pragma unroll
+  for (int k = 0; k < 8; k++) { const uint64_t t = (uint64_t)secp::N_HALF[k] - a.l[k] - br; br = (t >> 32) & 1; }
+  return br != 0; }
+// k_tx_finish for zkTxSenders, and beside it: a deposit's key rule; has_rec[i] (0 / 1: k_body_scatter replaces it by rec_of); the records of this workgroup in counts;
+// the first lane with status != OK in head[BH_FIRST_BAD] (the walk has set it to n).  Every lane reaches the one barrier.
+__global__ void __launch_bounds__(TX_THREADS) k_body_finish(uint32_t n, int homestead, const uint32_t *__restrict__ D, const uint32_t *__restrict__ E, const uint8_t *__restrict__ ok,
+                                                             const uint32_t *__restrict__ recovered, const uint32_t *__restrict__ rs, const uint32_t *__restrict__ xy, uint32_t *__restrict__ froms,
+                                                             uint8_t *__restrict__ status_out, uint8_t *__restrict__ code_out, int32_t *__restrict__ has_rec, uint32_t *__restrict__ counts,
+                                                             uint32_t *__restrict__ head, const uint32_t *__restrict__ sp_head) {
+  const uint32_t i = blockIdx.x * TX_THREADS + threadIdx.x; int has = 0;
+  if (i < n) {
+    if (i == 0) {                                                                                   // the recovery's four counters ride in the one download
+#pragma unroll
+      for (int k = 0; k < 4; k++) head[BH_WORDS + k] = sp_head[k]; }
+    const size_t nn = n; const uint32_t meta = D[TD_META * nn + i], code = (meta >> 8) & 0xFFu; uint32_t status = meta & 0xFFu; uint32_t f[5] = {0, 0, 0, 0, 0};
+    if (status == TX_OK) {
+      if (code == TX_DEPOSIT) {
+        // state_processor.go:141-146: addr1 = ExtractPKBAddress(HomesteadSigner{}, tx) must exist and equal addr2 = PubkeyToAddress({X, Y})
+        bool good = ok[i] != 0;                                                                     // recoverPlain (transaction_signing.go:246-271) over the six-field hash
+        if (good && !homestead) good = !above_half_n(secp::load_be(rs + 16 * (size_t)i + 8));      // :251 with homestead = true (crypto.go:205: s <= N / 2) where the call's recovery ran without it
+        good = good && E[TE_XY_OK * nn + i] != 0;                                                   // crypto.go:136-141: X or Y of more than 32 bytes kills a reference node; refused here
+        if (good) { uint32_t a[5]; secp::address_of(secp::load_be(xy + 16 * (size_t)i), secp::load_be(xy + 16 * (size_t)i + 8), a);   // crypto.go:212-215: Keccak256(pad32(X) || pad32(Y))[12:]
+#pragma unroll
+          for (int k = 0; k < 5; k++) good = good && a[k] == recovered[5 * (size_t)i + k]; }        // :144 addr1 != addr2; no curve check on (X, Y): the reference makes none
+        if (good) {
+#pragma unroll
+          for (int k = 0; k < 5; k++) f[k] = D[(TD_ZK + k) * nn + i]; }                             // Sender is ZKAdrress all the same (transaction_signing.go:72-76)
+        else status = TX_DEPOSIT_KEY;
+      }
+      else if (ok[i]) {
+#pragma unroll
+        for (int k = 0; k < 5; k++) f[k] = recovered[5 * (size_t)i + k]; }
+      else status = TX_SIG;                                                                         // whatever recoverPlain refuses
+    }
+#pragma unroll
+    for (int k = 0; k < 5; k++) froms[5 * (size_t)i + k] = f[k];
+    status_out[i] = (uint8_t)status; code_out[i] = (uint8_t)code;
+    has = status == TX_OK && body_kind1(code) != 0; has_rec[i] = has;
+    if (status != TX_OK) atomicMin(head + BH_FIRST_BAD, i);
+  }
+  const int count = __syncthreads_count(has);
+  if (threadIdx.x == 0) counts[blockIdx.x] = (uint32_t)count;
+}
+// an inclusive scan of one value a lane over a workgroup of T lanes through sh (T words); every lane calls it
+template <int T> __device__ __forceinline__ uint32_t block_scan_inclusive(uint32_t v, uint32_t *sh) {
+  sh[threadIdx.x] = v; __syncthreads();
+#pragma unroll
+  for (int d = 1; d < T; d <<= 1) { const uint32_t add = threadIdx.x >= (uint32_t)d ? sh[threadIdx.x - d] : 0u; __syncthreads(); v += add; sh[threadIdx.x] = v; __syncthreads(); }
+  return v;
+}
+// bases[b] = the records before workgroup b; head[BH_M] = m.  One workgroup; cdiv(nb, 256) tiles, a carry between them; the loop's bound is the same for every lane.
+__global__ void __launch_bounds__(BODY_SCAN_THREADS) k_body_scan(const uint32_t *__restrict__ counts, uint32_t nb, uint32_t *__restrict__ bases, uint32_t *__restrict__ head) {
+  __shared__ uint32_t sh[BODY_SCAN_THREADS]; uint32_t carry = 0;
+#pragma unroll 1
+  for (uint32_t base = 0; base < nb; base += BODY_SCAN_THREADS) {
+    const uint32_t b = base + threadIdx.x, v = b < nb ? counts[b] : 0u, incl = block_scan_inclusive<BODY_SCAN_THREADS>(v, sh);
+    if (b < nb) bases[b] = carry + incl - v;
+    carry += sh[BODY_SCAN_THREADS - 1]; __syncthreads();                                            // (sh is written again in the next turn)
+  }
+  if (threadIdx.x == 0) head[BH_M] = carry;
+}
+// prefix[i] = the records before transaction i, prefix[n] = m; rec_of[i] (it held has_rec[i]); src_of[j] = the transaction of record j; rec_froms[j] = froms of it
+__global__ void __launch_bounds__(TX_THREADS) k_body_scatter(uint32_t n, const uint32_t *__restrict__ bases, const uint32_t *__restrict__ froms, int32_t *__restrict__ rec_of,
+                                                              uint32_t *__restrict__ prefix, uint32_t *__restrict__ src_of, uint32_t *__restrict__ rec_froms) {
+  __shared__ uint32_t sh[TX_THREADS];
+  const uint32_t i = blockIdx.x * TX_THREADS + threadIdx.x, has = i < n ? (uint32_t)rec_of[i] : 0u, incl = block_scan_inclusive<TX_THREADS>(has, sh);
+  if (i >= n) return;                                                                              // (after the last barrier)
+  const uint32_t pre = bases[blockIdx.x] + incl - has;                                             // pre < m <= n where has is set
+  prefix[i] = pre; rec_of[i] = has ? (int32_t)pre : -1;
+  if (i == n - 1) prefix[n] = pre + has;
+  if (has) { src_of[pre] = i;
+#pragma unroll
+    for (int k = 0; k < 5; k++) rec_froms[5 * (size_t)pre + k] = froms[5 * (size_t)i + k]; }
+}
+// Four source bytes at byte offset a of the upload as a little-endian word.  ALIGNED: from one or two aligned words and a shift (the upload starts at an aligned
+// address and is padded to 8 bytes: the bytes of the second word that are shifted out lie inside it); otherwise four byte reads.  The caller has compared a + 3 with the
+// end of the field, which the walk has compared with the end of the transaction.
+template <bool ALIGNED> __device__ __forceinline__ uint32_t body_word(const uint8_t *__restrict__ up, uint64_t a) {
+  if constexpr (ALIGNED) {
+    const uint32_t *w = (const uint32_t *)up; const uint64_t k = a >> 2; const uint32_t sh = 8u * (uint32_t)(a & 3u); uint32_t v = w[k];
+    if (sh) v = (v >> sh) | (w[k + 1] << (32u - sh));
+    return v;
+  }
+  else return (uint32_t)up[a] | ((uint32_t)up[a + 1] << 8) | ((uint32_t)up[a + 2] << 16) | ((uint32_t)up[a + 3] << 24);
+}
+// A wave a record: word w of record j, w = lane, lane + 64, lane + 128 < 180, is written by one lane, whatever it holds — the kind, ZKValue, the proof's characters or
+// the zeros behind a short proof, an argument, a zero slot — so no byte of recs[0 .. m) is left as the allocation had it.  The fields in zk_verify_item's order
+// (zktx.go:122-133 mint, :148-160 send, :180-194 deposit, :198-210 redeem; state_processor.go:113, :124, :147, :158 for what the node passes).
+template <bool ALIGNED>
+__global__ void __launch_bounds__(BODY_GATHER_THREADS) k_body_gather(const uint8_t *__restrict__ up, const uint64_t *__restrict__ off, uint32_t n, const uint32_t *__restrict__ D,
+                                                                      const uint32_t *__restrict__ E, const uint32_t *__restrict__ recovered, const uint32_t *__restrict__ src_of,
+                                                                      const uint32_t *__restrict__ prefix, uint32_t *__restrict__ recs) {
+  const uint32_t j = (blockIdx.x * BODY_GATHER_THREADS + threadIdx.x) >> 6, lane = threadIdx.x & 63u;
+  if (j >= n || j >= prefix[n]) return;                                                            // (the whole wave: the grid is sized for n records, m is known on the device only)
+  const uint32_t i = src_of[j]; if (i >= n) return;
+  const size_t nn = n; const uint64_t o0 = off[i] - off[0]; const uint32_t code = (D[TD_META * nn + i] >> 8) & 0xFFu, kind1 = body_kind1(code);
+  const uint32_t pbeg = E[TE_PROOF * nn + i], psize = E[TE_PROOF_SIZE * nn + i], take = psize < 512u ? psize : 512u;   // the first 512 characters: verify* reads no more
+  const bool valued = code == 1 || code == 5, dep = code == TX_DEPOSIT, send = code == 2;
+#pragma unroll
+  for (uint32_t r = 0; r < 3; r++) {
+    const uint32_t w = lane + 64u * r; if (w >= (uint32_t)REC_WORDS) break;
+    uint32_t val = 0;
+    if (w == 0) val = kind1 - 1u;                                                                   // kind; reserved[0 .. 2] = 0 (word 1: reserved[3 .. 6] = 0)
+    else if (w == 2) val = valued ? E[TE_VAL_LO * nn + i] : 0u;                                     // value_s: ZKValue for mint and redeem, 0 otherwise
+    else if (w == 3) val = valued ? E[TE_VAL_HI * nn + i] : 0u;
+    else if (w >= 4 && w < 132) {
+      const uint32_t p = 4u * (w - 4u);
+      if (p + 4u <= take) val = body_word<ALIGNED>(up, o0 + pbeg + p);
+      else if (p < take) {                                                                          // the last characters of a proof shorter than 512: zero bytes behind them
+#pragma unroll
+        for (uint32_t k = 0; k < 3; k++) if (p + k < take) val |= (uint32_t)up[o0 + pbeg + p + k] << (8u * k); }
+    }
+    else if (w >= 132) {
+      const uint32_t a = (w - 132u) >> 3, q = (w - 132u) & 7u; uint32_t te = 0xFFFFFFFFu;           // which hash of the transaction is args[a]; none: zero
+      if (dep) { te = a == 0 ? TE_RT : a == 3 ? TE_SN : a == 4 ? TE_CMT : a == 5 ? TE_SNS : 0xFFFFFFFFu;   // RTcmt, pk, old, ZKSN, ZKCMT, ZKSNS
+        if (a == 1 && q < 5) val = recovered[5 * (size_t)i + q]; }                                  // the pk address: the recovered one, equal to PubkeyToAddress({X, Y}); twelve zero bytes behind it
+      else if (send) te = a == 1 ? TE_SN : a == 2 ? TE_CMTS : a == 3 ? TE_CMT : 0xFFFFFFFFu;        // old, ZKSN, ZKCMTS, ZKCMT
+      else te = a == 1 ? TE_SN : a == 2 ? TE_CMT : 0xFFFFFFFFu;                                     // old, ZKSN, ZKCMT
+      if (te != 0xFFFFFFFFu) val = body_word<ALIGNED>(up, o0 + E[te * nn + i] + 4u * q);            // (a hash has exactly 32 bytes: the walk refused every other length)
+    }
+    recs[(size_t)REC_WORDS * j + w] = val;
+  }
+}
+
 // ---- the host side ------------------------------------------------------------------------------------------------------------------------------------------------
 namespace {
 struct Txs : PinnedStage {                           // one a process, every member under the device mutex
@@ -281,7 +459,8 @@ size_t tx_sender_inputs(const uint8_t *txs, const uint64_t *off, size_t n, int s
   SyncAtExit sync;
   HIP_CHECK(hipMemcpyAsync(p, d.pin, up, hipMemcpyHostToDevice, s));
   const dim3 block(TX_THREADS), grid(cdiv(n, TX_THREADS)), grid2(cdiv(2 * n, TX_THREADS));
-  hipLaunchKernelGGL(k_tx_walk, grid, block, 0, s, dtx, doff, (uint32_t)n, signer, chain_id, D, (uint8_t *)rs, (uint8_t *)v, want_senders ? (uint8_t *)nullptr : d_sigs);
+  hipLaunchKernelGGL(k_tx_walk<false>, grid, block, 0, s, dtx, doff, (uint32_t)n, signer, chain_id, D, (uint8_t *)rs, (uint8_t *)v, want_senders ? (uint8_t *)nullptr : d_sigs,
+                     (uint32_t *)nullptr, (uint8_t *)nullptr, (uint32_t *)nullptr);
   hipLaunchKernelGGL(k_tx_hash, grid2, block, 0, s, dtx, doff, (uint32_t)n, chain_id, (const uint32_t *)D, want_senders ? hash : d_sighash, d_txhash);
   HIP_CHECK(hipGetLastError());
   if (want_senders) recover_senders_queue(hash, rs, (const uint8_t *)v, n, signer != SIGNER_FRONTIER, rec, s);
@@ -297,6 +476,57 @@ size_t tx_sender_inputs(const uint8_t *txs, const uint64_t *off, size_t n, int s
   const uint8_t *bst = back + 84 * n + 4 * ((65 * n + 3) / 4); memcpy(status, bst, n); memcpy(code, bst + 4 * okw, n);
   size_t good = 0; for (size_t i = 0; i < n; i++) good += status[i] == TX_OK;
   return good;
+}
+// zkTxRecords (include/zk_bodies.h).  The caller has checked the arguments and holds the device mutex.  One upload (txs, then off); the walk with both descriptors, the
+// hashes, the recovery's six launches once for all lanes, k_body_finish, k_body_scan, k_body_scatter, k_body_gather; four words that say m; one download: the small
+// outputs and recs[0 .. m).  rec_froms[m .. n) is zeroed, recs[m .. n) is not written.  first_bad: the first transaction with status != OK, n where there is none.
+// borders (may be null): n_borders transaction indices in 0 .. n; rec_borders[k] = the records before transaction borders[k].  Returns m.
+static bool g_gather_bytewise = false;                                                              // (zkgpu_test_bodies_gather: the measurement of DESIGN.md §23; under the device mutex)
+void tx_records_gather_bytewise(bool on) { g_gather_bytewise = on; }
+size_t tx_records(const uint8_t *txs, const uint64_t *off, size_t n, int signer, uint64_t chain_id, uint8_t *recs, uint8_t *rec_froms, int32_t *rec_of, uint8_t *txhash, uint8_t *froms,
+                  uint8_t *code, uint8_t *status, size_t *first_bad, const int *borders, size_t n_borders, int *rec_borders) {
+  if (!n) { if (first_bad) *first_bad = 0; for (size_t k = 0; k < n_borders; k++) rec_borders[k] = 0; return 0; }
+  if (n > 0x3FFFFFFFu) throw GpuError("txs: more than 2^30 - 1 transactions");
+  LaneScope lane(0); hipStream_t s = gpu().stream; Txs &d = txs_state();
+  // down, in words: head 8 (first_bad, m, -, -, the recovery's four) | txhash 8n | froms 5n | rec_froms 5n | rec_of n | prefix n + 1 | status | code | (to 8 bytes) | recs 180 m
+  const size_t okw = (n + 3) / 4, nb = cdiv(n, TX_THREADS), small_words = (2 * BH_WORDS + 20 * n + 1 + 2 * okw + 1) / 2 * 2, down_words = small_words + (size_t)REC_WORDS * n; uint8_t *back = nullptr;
+  const size_t up = stage(d, txs, off, n, 4 * down_words, &back), total8 = up - 8 * (n + 1);
+  // device, in words: up | D | E | hash 8n | rs 16n | xy 16n | v | the recovery's out | src_of n | counts nb | bases nb | (to 8 bytes) | down
+  const size_t w_up = up / 4, w_D = TD_WORDS * n, w_E = TE_WORDS * n, w_rec = recover_senders_out_words(n), before = (w_up + w_D + w_E + 40 * n + okw + w_rec + n + 2 * nb + 1) / 2 * 2;
+  d.grow(before + down_words + 2); uint32_t *p = d.io.get(); if (!p) throw GpuError("txs: no workspace");
+  const uint8_t *dtx = (const uint8_t *)p; const uint64_t *doff = (const uint64_t *)((const uint8_t *)p + total8);
+  uint32_t *D = p + w_up, *E = D + w_D, *hash = E + w_E, *rs = hash + 8 * n, *xy = rs + 16 * n, *v = xy + 16 * n, *rec = v + okw, *src_of = rec + w_rec, *counts = src_of + n, *bases = counts + nb, *dn = p + before;
+  uint32_t *d_head = dn, *d_txhash = dn + 2 * BH_WORDS, *d_froms = d_txhash + 8 * n, *d_rec_froms = d_froms + 5 * n, *d_rec_of = d_rec_froms + 5 * n, *d_prefix = d_rec_of + n;
+  uint8_t *d_status = (uint8_t *)(d_prefix + n + 1), *d_code = d_status + 4 * okw; uint32_t *d_recs = dn + small_words;      // (8-byte aligned: `before` and small_words are even)
+  SyncAtExit sync;
+  HIP_CHECK(hipMemcpyAsync(p, d.pin, up, hipMemcpyHostToDevice, s));
+  const dim3 block(TX_THREADS), grid(nb), grid2(cdiv(2 * n, TX_THREADS));
+  hipLaunchKernelGGL(k_tx_walk<true>, grid, block, 0, s, dtx, doff, (uint32_t)n, signer, chain_id, D, (uint8_t *)rs, (uint8_t *)v, (uint8_t *)nullptr, E, (uint8_t *)xy, d_head + BH_FIRST_BAD);
+  hipLaunchKernelGGL(k_tx_hash, grid2, block, 0, s, dtx, doff, (uint32_t)n, chain_id, (const uint32_t *)D, hash, d_txhash);
+  HIP_CHECK(hipGetLastError());
+  recover_senders_queue(hash, rs, (const uint8_t *)v, n, signer != SIGNER_FRONTIER, rec, s);       // once, for every lane; a deposit's Homestead rule where the flag is 0: k_body_finish
+  hipLaunchKernelGGL(k_body_finish, grid, block, 0, s, (uint32_t)n, (int)(signer != SIGNER_FRONTIER), (const uint32_t *)D, (const uint32_t *)E, (const uint8_t *)(rec + 4), (const uint32_t *)(rec + 4 + okw),
+                     (const uint32_t *)rs, (const uint32_t *)xy, d_froms, d_status, d_code, (int32_t *)d_rec_of, counts, d_head, (const uint32_t *)rec);
+  hipLaunchKernelGGL(k_body_scan, dim3(1), dim3(BODY_SCAN_THREADS), 0, s, (const uint32_t *)counts, (uint32_t)nb, bases, d_head);
+  hipLaunchKernelGGL(k_body_scatter, grid, block, 0, s, (uint32_t)n, (const uint32_t *)bases, (const uint32_t *)d_froms, (int32_t *)d_rec_of, d_prefix, src_of, d_rec_froms);
+  const dim3 gblock(BODY_GATHER_THREADS), ggrid(cdiv(64 * n, BODY_GATHER_THREADS));
+  if (g_gather_bytewise) hipLaunchKernelGGL(k_body_gather<false>, ggrid, gblock, 0, s, dtx, doff, (uint32_t)n, (const uint32_t *)D, (const uint32_t *)E, (const uint32_t *)(rec + 4 + okw), (const uint32_t *)src_of, (const uint32_t *)d_prefix, d_recs);
+  else hipLaunchKernelGGL(k_body_gather<true>, ggrid, gblock, 0, s, dtx, doff, (uint32_t)n, (const uint32_t *)D, (const uint32_t *)E, (const uint32_t *)(rec + 4 + okw), (const uint32_t *)src_of, (const uint32_t *)d_prefix, d_recs);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipMemcpyAsync(back, dn, 4 * BH_WORDS, hipMemcpyDeviceToHost, s)); HIP_CHECK(hipStreamSynchronize(s));   // m: the length of the download
+  uint32_t head[BH_WORDS]; memcpy(head, back, sizeof head); const size_t m = head[BH_M];
+  if (m > n || head[BH_FIRST_BAD] > n) throw GpuError("txs: the record count left by the device is out of range");
+  HIP_CHECK(hipMemcpyAsync(back, dn, 4 * (small_words + (size_t)REC_WORDS * m), hipMemcpyDeviceToHost, s)); HIP_CHECK(hipStreamSynchronize(s));
+  senders_keep_head((const uint32_t *)(back + 4 * BH_WORDS));
+  const uint8_t *b = back + 8 * BH_WORDS;
+  if (txhash) memcpy(txhash, b, 32 * n);
+  memcpy(froms, b + 32 * n, 20 * n); memcpy(rec_froms, b + 52 * n, 20 * m); memset(rec_froms + 20 * m, 0, 20 * (n - m)); memcpy(rec_of, b + 72 * n, 4 * n);
+  const uint32_t *prefix = (const uint32_t *)(b + 76 * n); const uint8_t *bst = b + 76 * n + 4 * (n + 1);
+  memcpy(status, bst, n); memcpy(code, bst + 4 * okw, n); if (m) memcpy(recs, back + 4 * small_words, 4 * (size_t)REC_WORDS * m);
+  if (prefix[n] != m) throw GpuError("txs: the prefix values left by the device do not end at the record count");
+  for (size_t k = 0; k < n_borders; k++) rec_borders[k] = (int)prefix[borders[k]];
+  if (first_bad) *first_bad = head[BH_FIRST_BAD];
+  return m;
 }
 // Keccak-256 of n byte strings, msgs[off[i] .. off[i+1]), through k_tx_hash's sponge
 void probe_keccak256(const uint8_t *msgs, const uint64_t *off, size_t n, uint8_t *out) {

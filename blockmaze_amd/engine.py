@@ -130,6 +130,19 @@ def tx_senders(txs, signer, chain_id, want_txhash=True):
     rc = int(lib().zkgpu_tx_senders(_bytes(blob), _u64p(off), n, int(signer), ctypes.c_uint64(chain_id), p("txhash"), p("froms"), p("code"), p("status")))
     return rc, o
 
+# records from the block bodies' bytes (csrc/gpu_txs.hip, csrc/capi_bodies.cpp; include/zk_bodies.h)
+TX_DEPOSIT_KEY = 4
+def tx_records(txs, signer, chain_id, want_txhash=True):
+    """zkgpu_tx_records -> (m or a ZKGPU_ERR_* code, dict of recs (n,) RECORD_DTYPE, rec_froms (n, 20), rec_of (n,) int32, txhash (n, 32) or None, froms (n, 20), code (n,),
+    status (n,)); every array is handed in full of 0xA5 bytes, so recs[m:] keeps them"""
+    n = len(txs); blob, off = _tx_blob(txs); o = {k: np.full((n, w) if w else n, 0xA5, dtype=np.uint8) for k, w in (("rec_froms", 20), ("txhash", 32), ("froms", 20), ("code", 0), ("status", 0))}
+    o["recs"] = np.frombuffer(bytes([0xA5]) * (720 * n), dtype=RECORD_DTYPE).copy(); o["rec_of"] = np.full(n, -1515870811, dtype=np.int32)
+    if not want_txhash: o["txhash"] = None
+    p = lambda k: o[k].ctypes.data_as(ctypes.c_void_p) if (n and o[k] is not None) else None
+    rc = int(lib().zkgpu_tx_records(_bytes(blob), _u64p(off), n, int(signer), ctypes.c_uint64(chain_id), p("recs"), p("rec_froms"), p("rec_of"), p("txhash"), p("froms"), p("code"), p("status")))
+    return rc, o
+def bodies_gather_bytewise(on): _check(lib().zkgpu_test_bodies_gather(int(bool(on))))   # test entry: k_body_gather's source reads, for the measurement of DESIGN.md §23
+
 def msm(group, points, scalars, window_bits=0, filter_ones=False):
     points = np.ascontiguousarray(points, dtype=np.uint64); scalars = np.ascontiguousarray(scalars, dtype=np.uint64); n = scalars.size // 4
     out = np.zeros(8 if group == 1 else 16, dtype=np.uint64)
@@ -900,5 +913,32 @@ class Zk:
         if rc < 0: raise ZkGpuError("zkTxSenders: %s" % self.L.zkgpu_last_error().decode())
         assert rc == int((st[:n, 0] == TX_OK).sum())
         return [bytes(fr[i]) for i in range(n)], ([bytes(th[i]) for i in range(n)] if want_txhash else None), [int(code[i, 0]) for i in range(n)], [int(st[i, 0]) for i in range(n)]
+    # include/zk_bodies.h: the records of a block body's transactions, and a stretch of the chain decided from the bodies' bytes
+    def TxRecords(self, txs, signer, chain_id, want_txhash=True):
+        """-> (recs: the m records as an array of RECORD_DTYPE, rec_froms: [20 bytes] x m, rec_of: [int] x n, froms: [20 bytes], txhash: [32 bytes] or None, code: [int],
+        status: [int]); raises ZkGpuError where the call returns -1"""
+        n = len(txs); blob, off = _tx_blob(txs); recs = np.zeros(max(1, n), dtype=RECORD_DTYPE); rf, th, fr, code, st = [np.zeros((max(1, n), w), dtype=np.uint8) for w in (20, 32, 20, 1, 1)]
+        of = np.zeros(max(1, n), dtype=np.int32); self.L.zkTxRecords.restype = ctypes.c_int
+        m = int(self.L.zkTxRecords(_bytes(blob), _u64p(off), n, int(signer), ctypes.c_uint64(chain_id), recs.ctypes.data_as(ctypes.c_void_p), _bytes(rf), of.ctypes.data_as(ctypes.c_void_p),
+                                   _bytes(th) if want_txhash else None, _bytes(fr), _bytes(code), _bytes(st)))
+        if m < 0: raise ZkGpuError("zkTxRecords: %s" % self.L.zkgpu_last_error().decode())
+        return (recs[:m].copy(), [bytes(rf[j]) for j in range(m)], [int(of[i]) for i in range(n)], [bytes(fr[i]) for i in range(n)], ([bytes(th[i]) for i in range(n)] if want_txhash else None),
+                [int(code[i, 0]) for i in range(n)], [int(st[i, 0]) for i in range(n)])
+    def VerifyChainBodies(self, cache, txs, block_first, signer, chain_id, a, tree, prior_anchors, window, s, fill=0):
+        """block_first: n_blocks + 1 TRANSACTION indices.  -> (blocks accepted or -1, dict of n_recs, recs (the m records, old slots filled), rec_froms, rec_of, froms, txhash,
+        code, status, ok [bool] x m, anchor_of [int] x m, accts_sizes, set_sizes (None without a set), tree_sizes); every output array is handed in full of `fill` bytes"""
+        n = len(txs); blob, off = _tx_blob(txs); bf = np.ascontiguousarray(block_first, dtype=np.int32).reshape(-1); nb = int(bf.size) - 1
+        pa = np.ascontiguousarray(prior_anchors if prior_anchors is not None else [], dtype=np.int64).reshape(-1); npa = int(pa.size)
+        recs = np.frombuffer(bytes([fill]) * (720 * max(1, n)), dtype=RECORD_DTYPE).copy(); rf, th, fr, code, st, ok = [np.full((max(1, n), w), fill, dtype=np.uint8) for w in (20, 32, 20, 1, 1, 1)]
+        of = np.full(max(1, n), -7, dtype=np.int32); an = np.full(max(1, n), -7, dtype=np.int32); sizes = [np.full(max(1, nb), -7, dtype=np.int64) for _ in range(3)]; m = ctypes.c_int(-7)
+        vp = lambda x: x.ctypes.data_as(ctypes.c_void_p); self.L.verifyChainBodies.restype = ctypes.c_int
+        rc = int(self.L.verifyChainBodies(_cache_handle(cache), _bytes(blob), _u64p(off), n, vp(bf) if nb >= 0 else None, nb, int(signer), ctypes.c_uint64(chain_id), _accts_handle(a),
+                                          ctypes.c_void_p(tree) if tree else None, vp(pa) if npa else None, npa, int(window), ctypes.c_void_p(s) if s else None, vp(recs), vp(rf), vp(of), vp(th), vp(fr),
+                                          vp(code), vp(st), vp(ok), vp(an), *[vp(x) for x in sizes], ctypes.byref(m)))
+        k = max(0, int(m.value)); out = [[int(x) for x in v[:nb]] if rc >= 0 else None for v in sizes]
+        return rc, dict(n_recs=int(m.value), recs=recs[:k].copy(), rec_froms=[bytes(rf[j]) for j in range(k)], rec_of=[int(of[i]) for i in range(n)], froms=[bytes(fr[i]) for i in range(n)],
+                        txhash=[bytes(th[i]) for i in range(n)], code=[int(code[i, 0]) for i in range(n)], status=[int(st[i, 0]) for i in range(n)], ok=[bool(ok[j, 0]) for j in range(k)],
+                        anchor_of=[int(an[j]) for j in range(k)], accts_sizes=out[0], set_sizes=(out[1] if s else None), tree_sizes=out[2],
+                        raw=dict(recs=recs, rec_froms=rf, rec_of=of, txhash=th, froms=fr, code=code, status=st, ok=ok, anchor_of=an))
     def VerifyDepositProofDepth(self, depth, proof, RT, pk, cmtb_old, sn_old, cmtb, sns):
         return bool(self.L.verifyDepositproofDepth(int(depth), proof.encode(), self.hx(RT), self.hx(pk), self.hx(cmtb_old), self.hx(sn_old), self.hx(cmtb), self.hx(sns)))

@@ -41,8 +41,8 @@
  * (:231-240; an unprotected V under EIP155 takes Homestead's road, :152-154).  Fields 1 to 6 are consecutive items of the input: the message is a fresh list
  * header, their bytes as they stand, and for EIP155 the canonical encoding of chain_id followed by 0x80 0x80.
  *
- * Not here: a chain call that takes transactions instead of froms; building the 720-byte records from a transaction's fields; the transaction trie root
- * (DeriveSha); signing; DepositTxV/R/S and ExtractPKBAddress; streaming a block body's outer list (the caller passes off); any change to the recovery.
+ * Not here: the transaction trie root (DeriveSha); signing; DepositTxV/R/S; streaming a block body's outer list (the caller passes off); any change to the
+ * recovery.  The records, a deposit's ExtractPKBAddress rule and a chain call that takes transactions are zk_bodies.h's.
  *
  * May be called from any thread; calls are served one at a time.  Exported by libzkgpu.so only: a caller that wants it adds -lzkgpu to its link line.
  */

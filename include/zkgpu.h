@@ -431,6 +431,16 @@ int zkgpu_tx_senders(const uint8_t *txs, const uint64_t *off /* n + 1 */, int n,
 /* test entry: out[i] = Keccak-256 (padding 0x01 ... 0x80, rate 136) of msgs[off[i] .. off[i+1]), n strings through k_tx_hash's sponge, one lane a string */
 int zkgpu_test_keccak256(const uint8_t *msgs, const uint64_t *off, size_t n, uint8_t *out /* n x 32 */);
 
+/* ---- records from the block bodies' bytes (the drop-in level is zk_bodies.h) --------------------------------------------------------------------
+ * zkgpu_tx_senders' road with the walk's second descriptor (the positions of the ZK fields; a deposit on HomesteadSigner's road), then k_body_finish (the deposit's
+ * key rule, the records of each workgroup), k_body_scan, k_body_scatter (rec_of, the prefix values, rec_froms) and k_body_gather (a wave a record).  One upload, four
+ * words that say m, one download with recs[0 .. m).  Takes the arguments of zkTxRecords (as flat arrays; recs: n x 720 bytes) and returns m, or ZKGPU_ERR_ARG (decided
+ * first, before the device is asked for), ZKGPU_ERR_NO_DEVICE, ZKGPU_ERR_RUNTIME; every output is zeroed on each of them.  txhash may be NULL. */
+int zkgpu_tx_records(const uint8_t *txs, const uint64_t *off /* n + 1 */, int n, int signer, uint64_t chain_id, zk_block_record *recs, uint8_t *rec_froms /* n x 20 */,
+                     int32_t *rec_of /* n */, uint8_t *txhash /* n x 32, or NULL */, uint8_t *froms /* n x 20 */, uint8_t *code, uint8_t *status);
+/* test entry: k_body_gather reads its source words bytewise (1) or from aligned words and a shift (0, the default) from the next call on: the measurement of §23 */
+int zkgpu_test_bodies_gather(int bytewise);
+
 #ifdef __cplusplus
 }
 #endif
