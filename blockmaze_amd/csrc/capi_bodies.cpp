@@ -1,6 +1,7 @@
 // extern "C" surface of the records from the block bodies' bytes and of the chain call on them (include/zk_bodies.h, include/zkgpu.h "Records from the block
 // bodies' bytes"): the arguments are checked here, before anything is queued; the device work is gpu_txs.hip's, the decision on the records is
-// verifyChainAccounts'.  Every C++ exception ends at this boundary.
+// verifyChainAccounts'.  verifyChainBodiesRoots (include/zk_tx_roots.h) is the same call with the headers' transaction roots.  Every C++ exception ends
+// at this boundary.
 #include <cstdio>
 #include <cstring>
 #include <mutex>
@@ -8,13 +9,16 @@
 #include <vector>
 #include "../../include/zkgpu.h"
 #include "../../include/zk_bodies.h"
+#include "../../include/zk_tx_roots.h"
 #include "gpu.hpp"
 
 extern std::mutex g_gpu_mutex;
 extern void zkgpu_set_error(const std::string &s);
 namespace zk {
 size_t tx_records(const uint8_t *txs, const uint64_t *off, size_t n, int signer, uint64_t chain_id, uint8_t *recs, uint8_t *rec_froms, int32_t *rec_of, uint8_t *txhash, uint8_t *froms,
-                  uint8_t *code, uint8_t *status, size_t *first_bad, const int *borders, size_t n_borders, int *rec_borders);
+                  uint8_t *code, uint8_t *status, size_t *first_bad, const int *borders, size_t n_borders, int *rec_borders, const int *block_first, size_t n_blocks, uint8_t *roots,
+                  uint8_t *defined);
+size_t trie_roots(const uint8_t *vals, const uint64_t *off, size_t n, const int *first, size_t n_lists, bool want_tx, uint8_t *roots, uint8_t *defined);
 void tx_records_gather_bytewise(bool on);
 }
 using namespace zk;
@@ -42,13 +46,18 @@ bool bodies_args_ok(const uint8_t *txs, const uint64_t *off, int n, int signer, 
   for (int i = 0; i < n; i++) if (off[i + 1] < off[i]) { zkgpu_set_error("bodies: offsets decrease"); return false; }
   return true;
 }
-// the device part under the device mutex: m, or ZKGPU_ERR_NO_DEVICE / ZKGPU_ERR_RUNTIME with every output zeroed
-int bodies_run(const uint8_t *txs, const uint64_t *off, int n, int signer, uint64_t chain_id, const BodyOut &o, size_t *first_bad, const int *borders, size_t n_borders, int *rec_borders) {
+// the device part under the device mutex: m, or ZKGPU_ERR_NO_DEVICE / ZKGPU_ERR_RUNTIME with every output zeroed.  roots (may be null): the transaction trie roots of
+// the n_blocks blocks between the borders, and defined, on the same upload; zeroed by the caller on an error.  n = 0 with roots: every block is empty, the trie's
+// finish launch alone.
+int bodies_run(const uint8_t *txs, const uint64_t *off, int n, int signer, uint64_t chain_id, const BodyOut &o, size_t *first_bad, const int *borders, size_t n_borders, int *rec_borders,
+               uint8_t *roots = nullptr, uint8_t *defined = nullptr) {
   int rc;
   try {
     if (!gpu_available()) { zkgpu_set_error(NO_DEVICE); rc = ZKGPU_ERR_NO_DEVICE; }
     else { std::lock_guard<std::mutex> lk(g_gpu_mutex);
-      rc = (int)tx_records(txs, off, (size_t)n, signer, chain_id, (uint8_t *)o.recs, o.rec_froms, o.rec_of, o.txhash, o.froms, o.code, o.status, first_bad, borders, n_borders, rec_borders); }
+      if (roots && !n) { trie_roots(txs, off, 0, borders, n_borders - 1, true, roots, defined); rc = 0; }
+      else rc = (int)tx_records(txs, off, (size_t)n, signer, chain_id, (uint8_t *)o.recs, o.rec_froms, o.rec_of, o.txhash, o.froms, o.code, o.status, first_bad, borders, n_borders, rec_borders,
+                                roots ? borders : nullptr, roots ? n_borders - 1 : 0, roots, defined); }
   }
   catch (const std::exception &e) { zkgpu_set_error(e.what()); rc = ZKGPU_ERR_RUNTIME; }
   catch (...) { zkgpu_set_error("unknown error"); rc = ZKGPU_ERR_RUNTIME; }
@@ -73,16 +82,20 @@ int zkTxRecords(const uint8_t *txs, const uint64_t *off, int n, int signer, uint
 }
 int zkgpu_test_bodies_gather(int bytewise) { std::lock_guard<std::mutex> lk(g_gpu_mutex); tx_records_gather_bytewise(bytewise != 0); return ZKGPU_OK; }
 
-int verifyChainBodies(zk_proof_cache *cache, const uint8_t *txs, const uint64_t *off, int n, const int *block_first, int n_blocks, int signer, uint64_t chain_id, zk_accts *accts,
-                      zk_tree *tree, const long long *prior_anchors, int n_prior, int window, zk_snset *set, zk_block_record *recs, uint8_t (*rec_froms)[20], int32_t *rec_of,
-                      uint8_t (*txhash)[32], uint8_t (*froms)[20], uint8_t *code, uint8_t *status, unsigned char *ok, int32_t *anchor_of, long long *accts_sizes, long long *set_sizes,
-                      long long *tree_sizes, int *n_recs) {
+}  // extern "C"
+
+// verifyChainBodies (with_roots false: the three last arguments are null and nothing of them is looked at) and verifyChainBodiesRoots
+static int chain_bodies(const char *name, bool with_roots, zk_proof_cache *cache, const uint8_t *txs, const uint64_t *off, int n, const int *block_first, int n_blocks, int signer, uint64_t chain_id,
+                        zk_accts *accts, zk_tree *tree, const long long *prior_anchors, int n_prior, int window, zk_snset *set, zk_block_record *recs, uint8_t (*rec_froms)[20], int32_t *rec_of,
+                        uint8_t (*txhash)[32], uint8_t (*froms)[20], uint8_t *code, uint8_t *status, unsigned char *ok, int32_t *anchor_of, long long *accts_sizes, long long *set_sizes,
+                        long long *tree_sizes, int *n_recs, const uint8_t (*want_roots)[32], uint8_t (*roots)[32], unsigned char *root_ok) {
   const BodyOut o = {recs, (uint8_t *)rec_froms, rec_of, (uint8_t *)txhash, (uint8_t *)froms, code, status};
   // every output zeroed; anchor_of: -1, "no anchor", as verifyChainAccounts leaves it.  The sizes arrays are not written: verifyChainAccounts may have reported the
   // sizes after an impossible rewind in their last entries (zk_accounts_chain.h).
   auto fail = [&](const std::string &why) {
-    zkgpu_set_error(why); fprintf(stderr, "libzkgpu: verifyChainBodies: %s\n", why.c_str());
+    zkgpu_set_error(why); fprintf(stderr, "libzkgpu: %s: %s\n", name, why.c_str());
     bodies_zero(n, o);
+    if (with_roots && n_blocks > 0) { if (roots) memset(roots, 0, 32 * (size_t)n_blocks); if (root_ok) memset(root_ok, 0, (size_t)n_blocks); }
     for (int i = 0; i < n; i++) { if (ok) ok[i] = 0; if (anchor_of) anchor_of[i] = -1; }
     if (n_recs) *n_recs = 0;
     return -1; };
@@ -96,15 +109,21 @@ int verifyChainBodies(zk_proof_cache *cache, const uint8_t *txs, const uint64_t 
     for (int b = 0; b < n_blocks; b++) if (block_first[b] > block_first[b + 1]) return fail("block_first decreases at block " + std::to_string(b));
     if (n_prior < 0 || (n_prior && !prior_anchors)) return fail("a negative number of prior anchors or a null pointer");
     if (window < 0) return fail("a negative window");
+    if (with_roots && n_blocks > 0 && (!want_roots || !roots || !root_ok)) return fail("a null pointer for the roots");
+    if (with_roots && n_blocks > 0 && !off) return fail("a null pointer");                         // (the roots of empty blocks still go through the upload: off[0] is read)
     if (!gpu_available()) return fail(NO_DEVICE);
     uint64_t tree_before = 0; if (zkgpu_tree_size((zkgpu_tree *)tree, &tree_before) != ZKGPU_OK) return fail(zkgpu_last_error());
     for (int a = 0; a < n_prior; a++) if (prior_anchors[a] < 0 || (uint64_t)prior_anchors[a] > tree_before) return fail("prior anchor " + std::to_string(a) + " is negative or above the tree's size");
     // 1. zkTxRecords on all n transactions; the records before each block border from the prefix values the device left
     std::vector<int> rec_first((size_t)n_blocks + 1, 0); size_t first_bad = 0; int m = 0;
-    if (n) { m = bodies_run(txs, off, n, signer, chain_id, o, &first_bad, block_first, (size_t)n_blocks + 1, rec_first.data()); if (m < 0) return fail(zkgpu_last_error()); }
-    // 2. B0: the first block that holds a transaction with status != ZK_TX_OK
+    //    (with the roots: DeriveSha of every block on the same upload, a block of no transactions included)
+    if (n || (with_roots && n_blocks)) { m = bodies_run(txs, off, n, signer, chain_id, o, &first_bad, block_first, (size_t)n_blocks + 1, rec_first.data(), with_roots ? (uint8_t *)roots : nullptr, root_ok);
+      if (m < 0) return fail(zkgpu_last_error()); }
+    // 2. B0: the first block that holds a transaction with status != ZK_TX_OK — or, with the roots, whose root is undefined or is not the header's (root_ok holds
+    //    "defined" here and "defined and equal" from here on)
     int B0 = n_blocks;
     if (n && first_bad < (size_t)n) { B0 = 0; while (B0 < n_blocks && (size_t)block_first[B0 + 1] <= first_bad) B0++; }
+    if (with_roots) for (int b = n_blocks - 1; b >= 0; b--) { root_ok[b] = root_ok[b] && memcmp(roots[b], want_roots[b], 32) == 0; if (!root_ok[b] && b < B0) B0 = b; }
     // 3. verifyChainAccounts on the records of blocks [0, B0); a refusal there has left the three states alone
     const int n0 = rec_first[B0];
     const int k = verifyChainAccounts(cache, recs, (const uint8_t (*)[20])rec_froms, n0, rec_first.data(), B0, accts, tree, prior_anchors, n_prior, window, set, ok, anchor_of, accts_sizes, set_sizes, tree_sizes);
@@ -121,5 +140,21 @@ int verifyChainBodies(zk_proof_cache *cache, const uint8_t *txs, const uint64_t 
   }
   catch (const std::exception &e) { return fail(e.what()); }
   catch (...) { return fail("unknown error"); }
+}
+
+extern "C" {
+int verifyChainBodies(zk_proof_cache *cache, const uint8_t *txs, const uint64_t *off, int n, const int *block_first, int n_blocks, int signer, uint64_t chain_id, zk_accts *accts,
+                      zk_tree *tree, const long long *prior_anchors, int n_prior, int window, zk_snset *set, zk_block_record *recs, uint8_t (*rec_froms)[20], int32_t *rec_of,
+                      uint8_t (*txhash)[32], uint8_t (*froms)[20], uint8_t *code, uint8_t *status, unsigned char *ok, int32_t *anchor_of, long long *accts_sizes, long long *set_sizes,
+                      long long *tree_sizes, int *n_recs) {
+  return chain_bodies("verifyChainBodies", false, cache, txs, off, n, block_first, n_blocks, signer, chain_id, accts, tree, prior_anchors, n_prior, window, set, recs, rec_froms, rec_of, txhash, froms,
+                      code, status, ok, anchor_of, accts_sizes, set_sizes, tree_sizes, n_recs, nullptr, nullptr, nullptr);
+}
+int verifyChainBodiesRoots(zk_proof_cache *cache, const uint8_t *txs, const uint64_t *off, int n, const int *block_first, int n_blocks, int signer, uint64_t chain_id, zk_accts *accts,
+                           zk_tree *tree, const long long *prior_anchors, int n_prior, int window, zk_snset *set, zk_block_record *recs, uint8_t (*rec_froms)[20], int32_t *rec_of,
+                           uint8_t (*txhash)[32], uint8_t (*froms)[20], uint8_t *code, uint8_t *status, unsigned char *ok, int32_t *anchor_of, long long *accts_sizes, long long *set_sizes,
+                           long long *tree_sizes, int *n_recs, const uint8_t (*want_roots)[32], uint8_t (*roots)[32], unsigned char *root_ok) {
+  return chain_bodies("verifyChainBodiesRoots", true, cache, txs, off, n, block_first, n_blocks, signer, chain_id, accts, tree, prior_anchors, n_prior, window, set, recs, rec_froms, rec_of, txhash,
+                      froms, code, status, ok, anchor_of, accts_sizes, set_sizes, tree_sizes, n_recs, want_roots, roots, root_ok);
 }
 }  // extern "C"

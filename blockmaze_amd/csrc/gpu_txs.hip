@@ -13,6 +13,10 @@
 //   k_body_scan     the exclusive scan of those counts, one workgroup
 //   k_body_scatter  rec_of, the n + 1 prefix values, the transaction of each record, rec_froms
 //   k_body_gather   a wave a record: the 180 words of a zk_block_record from the transaction's bytes
+// and, for zkTxRoots, verifyChainBodiesRoots and zkgpu_list_trie_roots (include/zk_tx_roots.h), on the same sponge
+//   k_trie_leaf     a lane a value: the hash of its leaf in the block's Merkle-Patricia trie (DeriveSha), at its position in the sorted order of the keys
+//   k_trie_level    once a key nibble depth, deepest first: the branch, and the extension around it, at the head of every run of keys that is one
+//   k_trie_finish   a lane a block: its root
 // Rules every kernel keeps: no lane waits for another lane; every loop is bounded by a constant or by the transaction's own length; every
 // offset taken from the input is checked against the end of its list — and so against the transaction's end — before the byte there is read; the Keccak state is
 // indexed by compile-time constants only; no kernel uses scratch.
@@ -424,6 +428,160 @@ __global__ void __launch_bounds__(BODY_GATHER_THREADS) k_body_gather(const uint8
   }
 }
 
+// ---- trie roots (include/zk_tx_roots.h) ------------------------------------------------------------------------------------------------------------
+// DeriveSha (core/types/derive_sha.go:32-41) of many lists at once.  The values of list b stand at the global positions first[b] .. first[b+1] - 1 in the order of their
+// keys; node holds 32 bytes a position.  k_trie_leaf writes every leaf's hash at its position, k_trie_level, once a key nibble depth and deepest first, replaces the hash
+// at the head of every run that is a branch at that depth by the hash of the branch (or of the extension around it), k_trie_finish takes position 0 of every list.
+// Every value has at least 32 bytes (the entries see to it), so every node is referenced by its hash (trie/hasher.go:176-178) and nothing is embedded.
+constexpr uint64_t NIB40 = 0xFFFFFFFFFFull;
+// rlp.Encode(uint(i)) (derive_sha.go:37) as nibbles (trie/encoding.go:65-75), left-aligned in 40 bits; *len: how many (2, 4, 6, 8 or 10)
+__device__ __forceinline__ uint64_t trie_key(uint32_t i, uint32_t *len) {
+  if (i < 0x80u) { *len = 2; return (uint64_t)(i ? i : 0x80u) << 32; }                              // 0 -> 80; 1 .. 7f -> the byte itself
+  const uint32_t c = i < 0x100u ? 1u : i < 0x10000u ? 2u : i < 0x1000000u ? 3u : 4u;                // 80 + c, then the c bytes
+  *len = 2 + 2 * c; return ((uint64_t)(0x80u + c) << 32) | ((uint64_t)i << (32 - 8 * c));
+}
+// the keys of a list of n values sorted as byte strings: the indices 1 .. min(n - 1, 127), then 0, then 128 .. n - 1
+__device__ __forceinline__ uint32_t trie_index_at(uint32_t s, uint32_t n) { const uint32_t m = n - 1 < 127u ? n - 1 : 127u; return s < m ? s + 1 : s == m ? 0u : s; }
+__device__ __forceinline__ uint32_t trie_pos_of(uint32_t i, uint32_t n) { const uint32_t m = n - 1 < 127u ? n - 1 : 127u; return i == 0 ? m : i < 128u ? i - 1 : i; }
+__device__ __forceinline__ uint64_t trie_key_at(uint32_t s, uint32_t n) { uint32_t l; return trie_key(trie_index_at(s, n), &l); }
+// two different keys: the nibbles they share (no key is a prefix of another, so they differ inside the shorter one); "they share d nibbles", d <= 10
+__device__ __forceinline__ int trie_cpl(uint64_t a, uint64_t b) { return (__clzll((long long)(a ^ b)) - 24) >> 2; }
+__device__ __forceinline__ bool trie_share(uint64_t a, uint64_t b, uint32_t d) { return ((a ^ b) >> (40u - 4u * d)) == 0; }
+// the first position in (p, hi] whose key does not share d nibbles with kp, the key at p; positions p .. hi - 1 of a list of n.  The keys that share a prefix are
+// consecutive, so a bisection finds it: at most 32 turns.
+__device__ __forceinline__ uint32_t trie_run_end(uint32_t p, uint64_t kp, uint32_t d, uint32_t hi, uint32_t n) {
+  uint32_t lo = p + 1;
+#pragma unroll 1
+  for (int it = 0; it < 32 && lo < hi; it++) { const uint32_t mid = lo + ((hi - lo) >> 1); if (trie_share(trie_key_at(mid, n), kp, d)) lo = mid + 1; else hi = mid; }
+  return lo;
+}
+// `count` (<= 8) bytes of v behind the len bytes of (lo, hi); bytes beyond 16 are dropped (the entries refuse the lengths that would need them)
+__device__ __forceinline__ void pre_append(uint64_t &lo, uint64_t &hi, uint32_t &len, uint64_t v, uint32_t count) {
+  if (len < 8) { lo |= v << (8 * len); if (len + count > 8) hi |= v >> (8 * (8 - len)); }           // (len + count > 8 with count <= 8 means len > 0: the shift is below 64)
+  else if (len < 16) hi |= v << (8 * (len - 8));
+  len += count;
+}
+// hexToCompact (trie/encoding.go:37-51) of the top `count` nibbles of nibs (left-aligned in 40 bits), as an RLP string in the low bytes of the result: a single byte
+// below 0x80 stands alone, otherwise 0x80 + length and the bytes; *len: its length, at most 7
+__device__ __forceinline__ uint64_t trie_compact_str(uint64_t nibs, uint32_t count, uint32_t term, uint32_t *len) {
+  const uint32_t odd = count & 1u, pairs = count >> 1; const uint64_t fb = ((uint64_t)((term << 1) | odd) << 4) | (odd ? nibs >> 36 : 0ull), rest = odd ? (nibs << 4) & NIB40 : nibs;
+  if (pairs == 0) { *len = 1; return fb; }                                                          // 0x00 .. 0x3f: its own encoding
+  uint64_t v = (0x81ull + pairs) | (fb << 8);
+#pragma unroll
+  for (uint32_t j = 0; j < 5; j++) if (j < pairs) v |= ((rest >> (32 - 8 * j)) & 0xFFull) << (8 * (2 + j));
+  *len = 2 + pairs; return v;
+}
+// A lane a value: the leaf [hexToCompact(the key from max(lam_s, lam_s+1) + 1 on, terminator set), value] through one sponge — list header || key string || string
+// header of the value in the prefix registers, then the value's bytes as they stand.  TXS: value i is transaction i of the walk that ran before; a malformed one marks
+// its block and is not hashed, a 0xC0 recipient is read as 0x80 (k_tx_hash's substitution).  first: n_lists + 1 entries from 0 to n, not decreasing (the host has checked).
+template <bool TXS>
+__global__ void __launch_bounds__(TX_THREADS) k_trie_leaf(const uint8_t *__restrict__ vals, const uint64_t *__restrict__ off, uint32_t n, const uint32_t *__restrict__ first, uint32_t n_lists,
+                                                           const uint32_t *__restrict__ D, uint32_t *__restrict__ blk_of, uint32_t *__restrict__ bad, uint64_t *__restrict__ node) {
+  const uint32_t i = blockIdx.x * TX_THREADS + threadIdx.x; if (i >= n) return;
+  uint32_t b = 0, hi = n_lists;                                                                     // the largest b with first[b] <= i: the one list with first[b] <= i < first[b+1]
+#pragma unroll 1
+  for (int it = 0; it < 32 && hi - b > 1; it++) { const uint32_t mid = b + ((hi - b) >> 1); if (first[mid] <= i) b = mid; else hi = mid; }
+  const uint32_t f = first[b], nb = first[b + 1] - f, s = trie_pos_of(i - f, nb); const size_t g = (size_t)f + s;
+  blk_of[g] = b;                                                                                    // (i -> g is a bijection inside a list)
+  const uint64_t len = off[i + 1] - off[i]; uint64_t sub = ~0ull; bool skip = len > 0xFFFFFFFFull - 16;   // (this library's bound: the three headers of such a leaf would not fit the prefix)
+  if constexpr (TXS) { const size_t nn = n; const uint32_t c0 = D[TD_C0 * nn + i];
+    if (skip || (D[TD_META * nn + i] & 0xFFu) == TX_MALFORMED) { atomicOr(bad + b, 1u); skip = true; }   // the body does not decode: the block has no root
+    else if (c0 != 0xFFFFFFFFu) sub = c0; }
+  if (skip) {
+#pragma unroll
+    for (int k = 0; k < 4; k++) node[4 * g + k] = 0ull;
+    return; }
+  uint32_t L; const uint64_t key = trie_key(i - f, &L);
+  const int lam_l = s ? trie_cpl(trie_key_at(s - 1, nb), key) : -1, lam_r = s + 1 < nb ? trie_cpl(key, trie_key_at(s + 1, nb)) : -1, lam = lam_l > lam_r ? lam_l : lam_r;
+  const uint32_t from = (uint32_t)(lam + 1);                                                        // from <= L: two keys share fewer nibbles than the shorter one has
+  uint32_t klen, c; const uint64_t kstr = trie_compact_str((key << (4 * from)) & NIB40, L - from, 1u, &klen);
+  uint64_t vh = 0x80ull + len; uint32_t vhl = 1;                                                    // (a one-byte value below 0x80 would stand alone: no value here has under 32 bytes)
+  if (len >= 56) { const uint64_t l = be_bytes(len, &c); vh = (0xB7ull + c) | (l << 8); vhl = 1 + c; }
+  const uint64_t payload = klen + vhl + len; uint64_t lh = 0xC0ull + payload; uint32_t lhl = 1;
+  if (payload >= 56) { const uint64_t l = be_bytes(payload, &c); lh = (0xF7ull + c) | (l << 8); lhl = 1 + c; }   // (c <= 5: the header fits eight bytes)
+  ByteSource m; m.pre_lo = m.pre_hi = m.suf_lo = m.suf_hi = 0; m.pre_len = m.suf_len = 0; m.src = vals + (off[i] - off[0]); m.src_len = len; m.sub = sub;
+  pre_append(m.pre_lo, m.pre_hi, m.pre_len, lh, lhl); pre_append(m.pre_lo, m.pre_hi, m.pre_len, kstr, klen); pre_append(m.pre_lo, m.pre_hi, m.pre_len, vh, vhl);
+  uint32_t h[8]; sponge256(m, 0x01u, h);
+#pragma unroll
+  for (int k = 0; k < 4; k++) node[4 * g + k] = (uint64_t)h[2 * k] | ((uint64_t)h[2 * k + 1] << 32);
+}
+// A lane a position, acting only at the head of a run of keys that share d nibbles and is a branch at depth d: two members or more, first and last sharing exactly d.
+// Its children are the heads of its at most sixteen (d + 1)-runs, found by bisection over positions; their hashes were written by the leaf launch or by a deeper
+// level.  The 17-item list (trie/node.go EncodeRLP: 0xA0 and 32 bytes for a child, 0x80 for none and for the value slot) goes through the sponge a piece at a time —
+// the state is indexed by constants only: the word in flight is XORed in through a chain of selects.  Where the larger adjacent prefix P at the run's two borders
+// leaves a gap, d > P + 1, the branch is wrapped in the extension [hexToCompact(nibbles P + 1 .. d - 1), hash].  The result replaces the hash at the head: nothing
+// outside the run reads or writes a position of the run in this launch.
+__global__ void __launch_bounds__(TX_THREADS) k_trie_level(uint32_t n, uint32_t d, const uint32_t *__restrict__ first, const uint32_t *__restrict__ blk_of, uint64_t *node) {
+  const uint32_t g = blockIdx.x * TX_THREADS + threadIdx.x; if (g >= n) return;
+  const uint32_t b = blk_of[g], f = first[b], nb = first[b + 1] - f, s = g - f;
+  uint32_t L; const uint64_t key = trie_key(trie_index_at(s, nb), &L); if (L <= d) return;
+  int lam_l = -1;
+  if (s) { const uint64_t kprev = trie_key_at(s - 1, nb); if (trie_share(kprev, key, d)) return; lam_l = trie_cpl(kprev, key); }   // not the head
+  const uint32_t e = trie_run_end(s, key, d, nb, nb); if (e - s < 2) return;
+  const uint64_t klast = trie_key_at(e - 1, nb); if (trie_share(klast, key, d + 1)) return;        // the branch lies deeper
+  const int lam_r = e < nb ? trie_cpl(klast, trie_key_at(e, nb)) : -1, P = lam_l > lam_r ? lam_l : lam_r;
+  uint32_t mask = 0, p = s;                                                                         // which of the sixteen children exist: nibble d of the head of each (d + 1)-run, ascending
+#pragma unroll 1
+  for (uint32_t c = 0; c < 16; c++) if (p < e) { const uint64_t kp = trie_key_at(p, nb); if (((kp >> (36u - 4u * d)) & 15u) == c) { mask |= 1u << c; p = trie_run_end(p, kp, d + 1, e, nb); } }
+  const uint32_t cnt = (uint32_t)__popc(mask), payload = 33u * cnt + (17u - cnt), H = payload < 256u ? 2u : 3u;   // cnt >= 2: the payload has 81 .. 529 bytes
+  const uint64_t hdr = payload < 256u ? (0xF8ull | ((uint64_t)payload << 8)) : (0xF9ull | ((uint64_t)(payload >> 8) << 8) | ((uint64_t)(payload & 0xFFu) << 16));
+  uint64_t st[25];
+#pragma unroll
+  for (int k = 0; k < 25; k++) st[k] = 0;
+  const uint32_t steps = H + 17u + 4u * cnt + 1u;                                                   // header bytes, seventeen item bytes, four words a child, the pad
+  uint32_t wi = 0, fill = 0, hdr_i = 0, c = 0, sub = 0; uint64_t acc = 0, h0 = 0, h1 = 0, h2 = 0, h3 = 0; p = s;
+#pragma unroll 1
+  for (uint32_t step = 0; step < steps; step++) {
+    const bool last = step + 1 == steps; uint64_t v; bool word = false;
+    if (last) v = 0x01ull;
+    else if (hdr_i < H) { v = (hdr >> (8 * hdr_i)) & 0xFFull; hdr_i++; }
+    else if (sub == 0) {
+      const bool present = c < 16 && ((mask >> c) & 1u); v = present ? 0xA0ull : 0x80ull;
+      if (present && p < e) { const uint64_t *q = node + 4 * ((size_t)f + p); h0 = q[0]; h1 = q[1]; h2 = q[2]; h3 = q[3];   // (p < e always: the first pass met the same heads)
+        p = trie_run_end(p, trie_key_at(p, nb), d + 1, e, nb); }
+      if (present) sub = 1; else c++;
+    }
+    else { v = sub == 1 ? h0 : sub == 2 ? h1 : sub == 3 ? h2 : h3; word = true; if (++sub == 5) { sub = 0; c++; } }
+    const uint64_t out = acc | (v << (8 * fill)); uint64_t carry = 0; bool full = true;               // fill < 8 at every turn
+    if (word) carry = fill ? v >> (64 - 8 * fill) : 0ull;
+    else { full = fill == 7 || last; fill = full ? 0 : fill + 1; }
+    if (full) {
+#pragma unroll
+      for (int k = 0; k < 17; k++) st[k] ^= (uint32_t)k == wi ? out : 0ull;
+      if (last) st[16] ^= 0x8000000000000000ull;
+      if (++wi == 17 || last) { secp::keccak_f1600(st); wi = 0; }
+      acc = carry;
+    }
+    else acc = out;
+  }
+  if ((int)d > P + 1) {                                                                             // trie.go:252-253: a short node leading up to the branch
+    const uint32_t from = (uint32_t)(P + 1), cn = d - from; uint32_t klen;
+    const uint64_t kstr = trie_compact_str((key << (4 * from)) & NIB40 & ~(NIB40 >> (4 * cn)), cn, 0u, &klen);   // cn <= 9, klen <= 6
+    const uint32_t pl = klen + 2, sh = 8 * pl; const uint64_t pre = (0xC0ull + klen + 33u) | (kstr << 8) | (0xA0ull << (8 * (1 + klen))), b0 = st[0], b1 = st[1], b2 = st[2], b3 = st[3];
+#pragma unroll
+    for (int k = 0; k < 25; k++) st[k] = 0;
+    if (pl == 8) { st[0] = pre; st[1] = b0; st[2] = b1; st[3] = b2; st[4] = b3; st[5] = 0x01ull; }
+    else { st[0] = pre | (b0 << sh); st[1] = (b0 >> (64 - sh)) | (b1 << sh); st[2] = (b1 >> (64 - sh)) | (b2 << sh); st[3] = (b2 >> (64 - sh)) | (b3 << sh); st[4] = (b3 >> (64 - sh)) | (0x01ull << sh); }
+    st[16] = 0x8000000000000000ull; secp::keccak_f1600(st);
+  }
+#pragma unroll
+  for (int k = 0; k < 4; k++) node[4 * (size_t)g + k] = st[k];
+}
+// A lane a list: emptyRoot (trie/trie.go:32) for no value, otherwise what stands at its position 0.  bad (the transaction forms): a list with a malformed
+// transaction has no root — 32 zero bytes, defined = 0.
+__global__ void __launch_bounds__(TX_THREADS) k_trie_finish(uint32_t n_lists, const uint32_t *__restrict__ first, const uint64_t *__restrict__ node, const uint32_t *__restrict__ bad,
+                                                             uint64_t *__restrict__ roots, uint8_t *__restrict__ defined) {
+  const uint32_t b = blockIdx.x * TX_THREADS + threadIdx.x; if (b >= n_lists) return;
+  const uint32_t f = first[b], nb = first[b + 1] - f; const bool good = !bad || bad[b] == 0;
+  uint64_t r[4] = {0xa655cc1b171fe856ull, 0x6ef8c092e64583ffull, 0xc0ad6c991be0485bull, 0x21b463e3b52f6201ull};
+  if (nb) {
+#pragma unroll
+    for (int k = 0; k < 4; k++) r[k] = node[4 * (size_t)f + k]; }
+#pragma unroll
+  for (int k = 0; k < 4; k++) roots[4 * (size_t)b + k] = good ? r[k] : 0ull;
+  if (defined) defined[b] = good ? 1 : 0;
+}
+
 // ---- the host side ------------------------------------------------------------------------------------------------------------------------------------------------
 namespace {
 struct Txs : PinnedStage {                           // one a process, every member under the device mutex
@@ -432,13 +590,59 @@ struct Txs : PinnedStage {                           // one a process, every mem
 };
 Txs &txs_state() { static Txs *t = new Txs; return *t; }   // (never destroyed: the runtime may be gone when statics are)
 size_t up8(size_t v) { return (v + 7) / 8 * 8; }
-// pinned: the bytes off[0] .. off[n) of the caller's buffer, padded to 8, then off itself; returns the bytes staged
-size_t stage(Txs &d, const uint8_t *bytes, const uint64_t *off, size_t n, size_t down_bytes, uint8_t **back) {
-  const size_t total = (size_t)(off[n] - off[0]), up = up8(total) + 8 * (n + 1);
+// pinned: the bytes off[0] .. off[n) of the caller's buffer, padded to 8, then off itself, then (the trie roots) the n_first entries of first as 32-bit words, padded
+// to 8; returns the bytes staged
+size_t stage(Txs &d, const uint8_t *bytes, const uint64_t *off, size_t n, size_t down_bytes, uint8_t **back, const int *first = nullptr, size_t n_first = 0) {
+  const size_t total = (size_t)(off[n] - off[0]), up0 = up8(total) + 8 * (n + 1), up = up0 + up8(4 * n_first);
   d.pinned(up + down_bytes); if (total) memcpy(d.pin, bytes + off[0], total); memset(d.pin + total, 0, up8(total) - total); memcpy(d.pin + up8(total), off, 8 * (n + 1));
+  if (n_first) { memcpy(d.pin + up0, first, 4 * n_first); memset(d.pin + up0 + 4 * n_first, 0, up8(4 * n_first) - 4 * n_first); }   // (checked by the caller: 0 .. n, so int and uint32_t agree)
   *back = d.pin + up; return up;
 }
+// The launches behind the upload: a leaf a value, a level for every nibble depth of the longest key — it depends on the largest list alone —, a root a list.  D: the
+// walk's descriptor (the transaction forms, with bad, n_lists words, and defined) or null.  node: 8 n words at an 8-byte boundary, roots: 8 n_lists words likewise.
+void trie_queue(const uint8_t *dvals, const uint64_t *doff, size_t n, const uint32_t *dfirst, size_t n_lists, size_t largest, const uint32_t *D, uint32_t *blk_of, uint32_t *bad, uint32_t *node,
+                uint32_t *roots, uint8_t *defined, hipStream_t s) {
+  const dim3 block(TX_THREADS);
+  if (D) HIP_CHECK(hipMemsetAsync(bad, 0, 4 * n_lists, s));
+  if (n) {
+    if (D) hipLaunchKernelGGL(k_trie_leaf<true>, dim3(cdiv(n, TX_THREADS)), block, 0, s, dvals, doff, (uint32_t)n, dfirst, (uint32_t)n_lists, D, blk_of, bad, (uint64_t *)node);
+    else hipLaunchKernelGGL(k_trie_leaf<false>, dim3(cdiv(n, TX_THREADS)), block, 0, s, dvals, doff, (uint32_t)n, dfirst, (uint32_t)n_lists, (const uint32_t *)nullptr, blk_of, (uint32_t *)nullptr, (uint64_t *)node);
+    const int nibbles = largest <= 1 ? 0 : largest <= 0x80 ? 2 : largest <= 0x100 ? 4 : largest <= 0x10000 ? 6 : largest <= 0x1000000 ? 8 : 10;   // of rlp(largest - 1); one value: no branch
+    for (int depth = nibbles - 1; depth >= 0; depth--) hipLaunchKernelGGL(k_trie_level, dim3(cdiv(n, TX_THREADS)), block, 0, s, (uint32_t)n, (uint32_t)depth, dfirst, (const uint32_t *)blk_of, (uint64_t *)node);
+  }
+  hipLaunchKernelGGL(k_trie_finish, dim3(cdiv(n_lists, TX_THREADS)), block, 0, s, (uint32_t)n_lists, dfirst, (const uint64_t *)node, D ? (const uint32_t *)bad : (const uint32_t *)nullptr, (uint64_t *)roots, defined);
+  HIP_CHECK(hipGetLastError());
+}
+size_t largest_list(const int *first, size_t n_lists) { size_t m = 0; for (size_t b = 0; b < n_lists; b++) m = std::max(m, (size_t)(first[b + 1] - first[b])); return m; }
+// device words behind a base for the trie's own arrays: blk_of n | bad n_lists | (to 8 bytes) | node 8n | roots 8 n_lists | defined, n_lists bytes (to 8 bytes)
+struct TrieWords { size_t blk_of, bad, node, roots, defined, end; };
+TrieWords trie_words(size_t base, size_t n, size_t n_lists) {
+  TrieWords w; w.blk_of = base; w.bad = w.blk_of + n; w.node = (w.bad + n_lists + 1) / 2 * 2; w.roots = w.node + 8 * n; w.defined = w.roots + 8 * n_lists; w.end = w.defined + (n_lists + 7) / 8 * 2; return w;
+}
 }  // namespace
+
+// zkgpu_list_trie_roots (want_tx false: the values verbatim) and zkgpu_tx_roots (want_tx: the walk first; defined is written).  The caller has checked the arguments
+// and holds the device mutex; n_lists > 0.  One upload (the bytes, off, first), one download (roots, then defined).  Returns the number of roots that are defined.
+size_t trie_roots(const uint8_t *vals, const uint64_t *off, size_t n, const int *first, size_t n_lists, bool want_tx, uint8_t *roots, uint8_t *defined) {
+  if (n > 0x3FFFFFFFu || n_lists > 0x3FFFFFFFu) throw GpuError("trie roots: more than 2^30 - 1 values or lists");
+  LaneScope lane(0); hipStream_t s = gpu().stream; Txs &d = txs_state(); uint8_t *back = nullptr;
+  const size_t down = 32 * n_lists + up8(n_lists), up = stage(d, vals, off, n, down, &back, first, n_lists + 1), total8 = up - 8 * (n + 1) - up8(4 * (n_lists + 1));
+  // device, in words: up | (the walk: D | rs 16n | v) | the trie's arrays
+  const size_t okw = (n + 3) / 4, w_walk = want_tx ? (TD_WORDS * n + 16 * n + okw + 1) / 2 * 2 : 0; const TrieWords w = trie_words(up / 4 + w_walk, n, n_lists);
+  d.grow(w.end + 2); uint32_t *p = d.io.get(); if (!p) throw GpuError("txs: no workspace");
+  const uint8_t *dvals = (const uint8_t *)p; const uint64_t *doff = (const uint64_t *)((const uint8_t *)p + total8); const uint32_t *dfirst = (const uint32_t *)(doff + n + 1);
+  uint32_t *D = p + up / 4, *rs = D + TD_WORDS * n, *v = rs + 16 * n;
+  SyncAtExit sync;
+  HIP_CHECK(hipMemcpyAsync(p, d.pin, up, hipMemcpyHostToDevice, s));
+  if (want_tx && n) hipLaunchKernelGGL(k_tx_walk<false>, dim3(cdiv(n, TX_THREADS)), dim3(TX_THREADS), 0, s, dvals, doff, (uint32_t)n, (int)SIGNER_FRONTIER, (uint64_t)0, D, (uint8_t *)rs, (uint8_t *)v,
+                                       (uint8_t *)nullptr, (uint32_t *)nullptr, (uint8_t *)nullptr, (uint32_t *)nullptr);   // (MALFORMED and the 0xC0 position depend on no signer)
+  trie_queue(dvals, doff, n, dfirst, n_lists, largest_list(first, n_lists), want_tx ? (const uint32_t *)D : (const uint32_t *)nullptr, p + w.blk_of, p + w.bad, p + w.node, p + w.roots,
+             want_tx ? (uint8_t *)(p + w.defined) : (uint8_t *)nullptr, s);
+  HIP_CHECK(hipMemcpyAsync(back, p + w.roots, want_tx ? down : 32 * n_lists, hipMemcpyDeviceToHost, s)); HIP_CHECK(hipStreamSynchronize(s));
+  memcpy(roots, back, 32 * n_lists); size_t good = n_lists;
+  if (want_tx) { memcpy(defined, back + 32 * n_lists, n_lists); good = 0; for (size_t b = 0; b < n_lists; b++) good += defined[b] != 0; }
+  return good;
+}
 
 // The caller has checked the arguments and holds the device mutex.  want_senders: zkTxSenders (sighash, sigs, deposit_from null), else zkTxSigningInputs.
 // One upload (txs, then off), three launches — nine with the recovery — and one download.  Returns the number of records with status OK.
@@ -481,19 +685,25 @@ size_t tx_sender_inputs(const uint8_t *txs, const uint64_t *off, size_t n, int s
 // hashes, the recovery's six launches once for all lanes, k_body_finish, k_body_scan, k_body_scatter, k_body_gather; four words that say m; one download: the small
 // outputs and recs[0 .. m).  rec_froms[m .. n) is zeroed, recs[m .. n) is not written.  first_bad: the first transaction with status != OK, n where there is none.
 // borders (may be null): n_borders transaction indices in 0 .. n; rec_borders[k] = the records before transaction borders[k].  Returns m.
+// roots (may be null; verifyChainBodiesRoots): the transaction trie roots of the n_blocks blocks that block_first names, and defined, as zkTxRoots writes
+// them — block_first rides in the same upload, the trie's launches follow the hashes on the walk's descriptor, the roots come down with the records.  Without roots
+// nothing of this is queued and the launches are the ones zkTxRecords and verifyChainBodies have always made.
 static bool g_gather_bytewise = false;                                                              // (zkgpu_test_bodies_gather: the measurement of DESIGN.md §23; under the device mutex)
 void tx_records_gather_bytewise(bool on) { g_gather_bytewise = on; }
 size_t tx_records(const uint8_t *txs, const uint64_t *off, size_t n, int signer, uint64_t chain_id, uint8_t *recs, uint8_t *rec_froms, int32_t *rec_of, uint8_t *txhash, uint8_t *froms,
-                  uint8_t *code, uint8_t *status, size_t *first_bad, const int *borders, size_t n_borders, int *rec_borders) {
+                  uint8_t *code, uint8_t *status, size_t *first_bad, const int *borders, size_t n_borders, int *rec_borders, const int *block_first, size_t n_blocks, uint8_t *roots,
+                  uint8_t *defined) {
   if (!n) { if (first_bad) *first_bad = 0; for (size_t k = 0; k < n_borders; k++) rec_borders[k] = 0; return 0; }
   if (n > 0x3FFFFFFFu) throw GpuError("txs: more than 2^30 - 1 transactions");
   LaneScope lane(0); hipStream_t s = gpu().stream; Txs &d = txs_state();
   // down, in words: head 8 (first_bad, m, -, -, the recovery's four) | txhash 8n | froms 5n | rec_froms 5n | rec_of n | prefix n + 1 | status | code | (to 8 bytes) | recs 180 m
   const size_t okw = (n + 3) / 4, nb = cdiv(n, TX_THREADS), small_words = (2 * BH_WORDS + 20 * n + 1 + 2 * okw + 1) / 2 * 2, down_words = small_words + (size_t)REC_WORDS * n; uint8_t *back = nullptr;
-  const size_t up = stage(d, txs, off, n, 4 * down_words, &back), total8 = up - 8 * (n + 1);
+  const size_t n_first = roots ? n_blocks + 1 : 0, roots_down = roots ? 32 * n_blocks + up8(n_blocks) : 0;
+  const size_t up = stage(d, txs, off, n, 4 * down_words + roots_down, &back, block_first, n_first), total8 = up - 8 * (n + 1) - up8(4 * n_first);
   // device, in words: up | D | E | hash 8n | rs 16n | xy 16n | v | the recovery's out | src_of n | counts nb | bases nb | (to 8 bytes) | down
   const size_t w_up = up / 4, w_D = TD_WORDS * n, w_E = TE_WORDS * n, w_rec = recover_senders_out_words(n), before = (w_up + w_D + w_E + 40 * n + okw + w_rec + n + 2 * nb + 1) / 2 * 2;
-  d.grow(before + down_words + 2); uint32_t *p = d.io.get(); if (!p) throw GpuError("txs: no workspace");
+  const TrieWords tw = trie_words((before + down_words + 1) / 2 * 2, roots ? n : 0, roots ? n_blocks : 0);   // (behind the download; nothing where no roots are asked for)
+  d.grow(tw.end + 2); uint32_t *p = d.io.get(); if (!p) throw GpuError("txs: no workspace");
   const uint8_t *dtx = (const uint8_t *)p; const uint64_t *doff = (const uint64_t *)((const uint8_t *)p + total8);
   uint32_t *D = p + w_up, *E = D + w_D, *hash = E + w_E, *rs = hash + 8 * n, *xy = rs + 16 * n, *v = xy + 16 * n, *rec = v + okw, *src_of = rec + w_rec, *counts = src_of + n, *bases = counts + nb, *dn = p + before;
   uint32_t *d_head = dn, *d_txhash = dn + 2 * BH_WORDS, *d_froms = d_txhash + 8 * n, *d_rec_froms = d_froms + 5 * n, *d_rec_of = d_rec_froms + 5 * n, *d_prefix = d_rec_of + n;
@@ -504,6 +714,8 @@ size_t tx_records(const uint8_t *txs, const uint64_t *off, size_t n, int signer,
   hipLaunchKernelGGL(k_tx_walk<true>, grid, block, 0, s, dtx, doff, (uint32_t)n, signer, chain_id, D, (uint8_t *)rs, (uint8_t *)v, (uint8_t *)nullptr, E, (uint8_t *)xy, d_head + BH_FIRST_BAD);
   hipLaunchKernelGGL(k_tx_hash, grid2, block, 0, s, dtx, doff, (uint32_t)n, chain_id, (const uint32_t *)D, hash, d_txhash);
   HIP_CHECK(hipGetLastError());
+  if (roots) trie_queue(dtx, doff, n, (const uint32_t *)(doff + n + 1), n_blocks, largest_list(block_first, n_blocks), (const uint32_t *)D, p + tw.blk_of, p + tw.bad, p + tw.node, p + tw.roots,
+                        (uint8_t *)(p + tw.defined), s);
   recover_senders_queue(hash, rs, (const uint8_t *)v, n, signer != SIGNER_FRONTIER, rec, s);       // once, for every lane; a deposit's Homestead rule where the flag is 0: k_body_finish
   hipLaunchKernelGGL(k_body_finish, grid, block, 0, s, (uint32_t)n, (int)(signer != SIGNER_FRONTIER), (const uint32_t *)D, (const uint32_t *)E, (const uint8_t *)(rec + 4), (const uint32_t *)(rec + 4 + okw),
                      (const uint32_t *)rs, (const uint32_t *)xy, d_froms, d_status, d_code, (int32_t *)d_rec_of, counts, d_head, (const uint32_t *)rec);
@@ -516,7 +728,10 @@ size_t tx_records(const uint8_t *txs, const uint64_t *off, size_t n, int signer,
   HIP_CHECK(hipMemcpyAsync(back, dn, 4 * BH_WORDS, hipMemcpyDeviceToHost, s)); HIP_CHECK(hipStreamSynchronize(s));   // m: the length of the download
   uint32_t head[BH_WORDS]; memcpy(head, back, sizeof head); const size_t m = head[BH_M];
   if (m > n || head[BH_FIRST_BAD] > n) throw GpuError("txs: the record count left by the device is out of range");
-  HIP_CHECK(hipMemcpyAsync(back, dn, 4 * (small_words + (size_t)REC_WORDS * m), hipMemcpyDeviceToHost, s)); HIP_CHECK(hipStreamSynchronize(s));
+  HIP_CHECK(hipMemcpyAsync(back, dn, 4 * (small_words + (size_t)REC_WORDS * m), hipMemcpyDeviceToHost, s));
+  if (roots) HIP_CHECK(hipMemcpyAsync(back + 4 * down_words, p + tw.roots, roots_down, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  if (roots) { memcpy(roots, back + 4 * down_words, 32 * n_blocks); memcpy(defined, back + 4 * down_words + 32 * n_blocks, n_blocks); }
   senders_keep_head((const uint32_t *)(back + 4 * BH_WORDS));
   const uint8_t *b = back + 8 * BH_WORDS;
   if (txhash) memcpy(txhash, b, 32 * n);

@@ -143,6 +143,24 @@ def tx_records(txs, signer, chain_id, want_txhash=True):
     return rc, o
 def bodies_gather_bytewise(on): _check(lib().zkgpu_test_bodies_gather(int(bool(on))))   # test entry: k_body_gather's source reads, for the measurement of DESIGN.md §23
 
+# trie roots of many lists (csrc/gpu_txs.hip, csrc/capi_tx_roots.cpp; include/zk_tx_roots.h)
+def _first(lists_first): return np.ascontiguousarray(lists_first, dtype=np.int32).reshape(-1)
+def _i32p(a): return a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+def list_trie_roots(vals, first, start=0):
+    """zkgpu_list_trie_roots: DeriveSha of every list; vals: byte strings taken verbatim, first: n_lists + 1 indices into vals; start: the blob begins at this byte of
+    its buffer (off[0] = start).  -> (ZKGPU_OK or a ZKGPU_ERR_* code, roots (n_lists, 32) uint8, handed in full of 0xA5)"""
+    n = len(vals); blob, off = _tx_blob(vals); f = _first(first); nl = int(f.size) - 1
+    if start: blob = np.concatenate([np.zeros(start, dtype=np.uint8), blob]); off = off + np.uint64(start)
+    roots = np.full((max(0, nl), 32), 0xA5, dtype=np.uint8)
+    rc = int(lib().zkgpu_list_trie_roots(_bytes(blob), _u64p(off), n, _i32p(f), nl, _bytes(roots) if nl > 0 else None))
+    return rc, roots
+def tx_roots(txs, block_first):
+    """zkgpu_tx_roots -> (the number of defined roots or a ZKGPU_ERR_* code, roots (n_blocks, 32) uint8, defined (n_blocks,) uint8), both handed in full of 0xA5"""
+    n = len(txs); blob, off = _tx_blob(txs); f = _first(block_first); nb = int(f.size) - 1
+    roots = np.full((max(0, nb), 32), 0xA5, dtype=np.uint8); defined = np.full(max(0, nb), 0xA5, dtype=np.uint8)
+    rc = int(lib().zkgpu_tx_roots(_bytes(blob), _u64p(off), n, _i32p(f), nb, _bytes(roots) if nb > 0 else None, _bytes(defined) if nb > 0 else None))
+    return rc, roots, defined
+
 def msm(group, points, scalars, window_bits=0, filter_ones=False):
     points = np.ascontiguousarray(points, dtype=np.uint64); scalars = np.ascontiguousarray(scalars, dtype=np.uint64); n = scalars.size // 4
     out = np.zeros(8 if group == 1 else 16, dtype=np.uint64)
@@ -940,5 +958,32 @@ class Zk:
                         txhash=[bytes(th[i]) for i in range(n)], code=[int(code[i, 0]) for i in range(n)], status=[int(st[i, 0]) for i in range(n)], ok=[bool(ok[j, 0]) for j in range(k)],
                         anchor_of=[int(an[j]) for j in range(k)], accts_sizes=out[0], set_sizes=(out[1] if s else None), tree_sizes=out[2],
                         raw=dict(recs=recs, rec_froms=rf, rec_of=of, txhash=th, froms=fr, code=code, status=st, ok=ok, anchor_of=an))
+    # include/zk_tx_roots.h: the transaction trie roots of a segment's bodies, and the chain call that holds them against the headers' roots
+    def TxRoots(self, txs, block_first):
+        """-> (roots: [32 bytes] x n_blocks, defined: [bool] x n_blocks); raises ZkGpuError where the call returns -1"""
+        n = len(txs); blob, off = _tx_blob(txs); bf = _first(block_first); nb = int(bf.size) - 1
+        roots = np.zeros((max(1, nb), 32), dtype=np.uint8); defined = np.zeros(max(1, nb), dtype=np.uint8); self.L.zkTxRoots.restype = ctypes.c_int
+        rc = int(self.L.zkTxRoots(_bytes(blob), _u64p(off), n, _i32p(bf), nb, _bytes(roots), _bytes(defined)))
+        if rc < 0: raise ZkGpuError("zkTxRoots: %s" % self.L.zkgpu_last_error().decode())
+        assert rc == int(defined[:nb].sum())
+        return [bytes(roots[b]) for b in range(nb)], [bool(defined[b]) for b in range(nb)]
+    def VerifyChainBodiesRoots(self, cache, txs, block_first, want_roots, signer, chain_id, a, tree, prior_anchors, window, s, fill=0):
+        """VerifyChainBodies with want_roots: [32 bytes] x n_blocks (header.TxHash of each block).  -> (blocks accepted or -1, VerifyChainBodies' dict and roots: [32 bytes] x
+        n_blocks, root_ok: [bool] x n_blocks)"""
+        n = len(txs); blob, off = _tx_blob(txs); bf = _first(block_first); nb = int(bf.size) - 1
+        pa = np.ascontiguousarray(prior_anchors if prior_anchors is not None else [], dtype=np.int64).reshape(-1); npa = int(pa.size)
+        recs = np.frombuffer(bytes([fill]) * (720 * max(1, n)), dtype=RECORD_DTYPE).copy(); rf, th, fr, code, st, ok = [np.full((max(1, n), w), fill, dtype=np.uint8) for w in (20, 32, 20, 1, 1, 1)]
+        of = np.full(max(1, n), -7, dtype=np.int32); an = np.full(max(1, n), -7, dtype=np.int32); sizes = [np.full(max(1, nb), -7, dtype=np.int64) for _ in range(3)]; m = ctypes.c_int(-7)
+        want = np.frombuffer(b"".join(bytes(r) for r in want_roots) or bytes(32), dtype=np.uint8).copy(); roots = np.full((max(1, nb), 32), fill, dtype=np.uint8); rok = np.full(max(1, nb), fill, dtype=np.uint8)
+        vp = lambda x: x.ctypes.data_as(ctypes.c_void_p); self.L.verifyChainBodiesRoots.restype = ctypes.c_int
+        rc = int(self.L.verifyChainBodiesRoots(_cache_handle(cache), _bytes(blob), _u64p(off), n, vp(bf) if nb >= 0 else None, nb, int(signer), ctypes.c_uint64(chain_id), _accts_handle(a),
+                                               ctypes.c_void_p(tree) if tree else None, vp(pa) if npa else None, npa, int(window), ctypes.c_void_p(s) if s else None, vp(recs), vp(rf), vp(of), vp(th),
+                                               vp(fr), vp(code), vp(st), vp(ok), vp(an), *[vp(x) for x in sizes], ctypes.byref(m), vp(want), vp(roots), vp(rok)))
+        k = max(0, int(m.value)); out = [[int(x) for x in v[:nb]] if rc >= 0 else None for v in sizes]
+        return rc, dict(n_recs=int(m.value), recs=recs[:k].copy(), rec_froms=[bytes(rf[j]) for j in range(k)], rec_of=[int(of[i]) for i in range(n)], froms=[bytes(fr[i]) for i in range(n)],
+                        txhash=[bytes(th[i]) for i in range(n)], code=[int(code[i, 0]) for i in range(n)], status=[int(st[i, 0]) for i in range(n)], ok=[bool(ok[j, 0]) for j in range(k)],
+                        anchor_of=[int(an[j]) for j in range(k)], accts_sizes=out[0], set_sizes=(out[1] if s else None), tree_sizes=out[2],
+                        roots=[bytes(roots[b]) for b in range(max(0, nb))], root_ok=[bool(rok[b]) for b in range(max(0, nb))],
+                        raw=dict(recs=recs, rec_froms=rf, rec_of=of, txhash=th, froms=fr, code=code, status=st, ok=ok, anchor_of=an, roots=roots, root_ok=rok))
     def VerifyDepositProofDepth(self, depth, proof, RT, pk, cmtb_old, sn_old, cmtb, sns):
         return bool(self.L.verifyDepositproofDepth(int(depth), proof.encode(), self.hx(RT), self.hx(pk), self.hx(cmtb_old), self.hx(sn_old), self.hx(cmtb), self.hx(sns)))

@@ -38,7 +38,7 @@
  * proof: the first 512 bytes of ZKProof where it has at least 512 (verify* reads only those), otherwise its bytes followed by zero bytes; a zero byte is no hex
  * digit, so such a record is rejected by the proof step.
  *
- * Not here: records handed to the chain call without the trip through recs; the transaction trie root (DeriveSha); DepositTxV/R/S (no reference code path reads them
+ * Not here: records handed to the chain call without the trip through recs; DepositTxV/R/S (no reference code path reads them
  * on import); a pool form; a miner's drop-and-go-on; streaming a body's outer list; nonce, balance and gas rules of public transactions; any change to the recovery
  * or to verifyChainAccounts.
  *

@@ -441,6 +441,21 @@ int zkgpu_tx_records(const uint8_t *txs, const uint64_t *off /* n + 1 */, int n,
 /* test entry: k_body_gather reads its source words bytewise (1) or from aligned words and a shift (0, the default) from the next call on: the measurement of §23 */
 int zkgpu_test_bodies_gather(int bytewise);
 
+/* ---- trie roots of many lists (the drop-in level is zk_tx_roots.h) ----------------------------------------------------------------------------
+ * DeriveSha (core/types/derive_sha.go:32-41) of n_lists DerivableLists in one call: list l holds the values first[l] .. first[l+1] - 1 (n_lists + 1 entries, from 0
+ * to n, not decreasing), value i is vals[off[i] .. off[i+1]) and is taken verbatim — no walk, no substitution —, its key is rlp(its index within its list).
+ * k_trie_leaf (a lane a value: the one pass over the bytes), k_trie_level once per key nibble depth, deepest first, k_trie_finish (a lane a list).  roots: n_lists
+ * x 32, emptyRoot for a list with no value.  One upload, one download.  A value under 32 bytes gives ZKGPU_ERR_ARG: a leaf under 32 bytes would be embedded in its
+ * parent (trie/hasher.go:176-178) and the kernels reference every node by hash; transactions that decode (five 32-byte hashes) and receipts (a 256-byte bloom)
+ * never are.  Also ZKGPU_ERR_ARG (decided first, before the device is asked for): a negative count, a null pointer with n > 0 or n_lists > 0, a decreasing off, a
+ * value of 2^32 - 16 bytes or more (the leaf's three headers fit the sponge's sixteen prefix bytes below that), a first that does not run from 0 to n.  ZKGPU_ERR_NO_DEVICE, ZKGPU_ERR_RUNTIME; roots is zeroed on every error.  n_lists = 0
+ * returns ZKGPU_OK and queues nothing. */
+int zkgpu_list_trie_roots(const uint8_t *vals, const uint64_t *off /* n + 1 */, int n, const int *first /* n_lists + 1 */, int n_lists, uint8_t *roots /* n_lists x 32 */);
+/* zkTxRoots (zk_tx_roots.h) with flat arrays: the walk, then the same three steps with a 0xC0 recipient read as 0x80; defined[b] = 0 and a zero root for a block
+ * with a malformed transaction.  Returns the number of defined roots, or ZKGPU_ERR_ARG / ZKGPU_ERR_NO_DEVICE / ZKGPU_ERR_RUNTIME with both outputs zeroed. */
+int zkgpu_tx_roots(const uint8_t *txs, const uint64_t *off /* n + 1 */, int n, const int *block_first /* n_blocks + 1 */, int n_blocks, uint8_t *roots /* n_blocks x 32 */,
+                   uint8_t *defined /* n_blocks */);
+
 #ifdef __cplusplus
 }
 #endif
