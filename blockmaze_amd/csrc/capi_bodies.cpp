@@ -4,28 +4,13 @@
 // at this boundary.
 #include <cstdio>
 #include <cstring>
-#include <mutex>
-#include <string>
 #include <vector>
-#include "../../include/zkgpu.h"
 #include "../../include/zk_bodies.h"
 #include "../../include/zk_tx_roots.h"
-#include "gpu.hpp"
-
-extern std::mutex g_gpu_mutex;
-extern void zkgpu_set_error(const std::string &s);
-namespace zk {
-size_t tx_records(const uint8_t *txs, const uint64_t *off, size_t n, int signer, uint64_t chain_id, uint8_t *recs, uint8_t *rec_froms, int32_t *rec_of, uint8_t *txhash, uint8_t *froms,
-                  uint8_t *code, uint8_t *status, size_t *first_bad, const int *borders, size_t n_borders, int *rec_borders, const int *block_first, size_t n_blocks, uint8_t *roots,
-                  uint8_t *defined);
-size_t trie_roots(const uint8_t *vals, const uint64_t *off, size_t n, const int *first, size_t n_lists, bool want_tx, uint8_t *roots, uint8_t *defined);
-void tx_records_gather_bytewise(bool on);
-}
+#include "txs_host.hpp"
 using namespace zk;
 
 namespace {
-const char *const NO_DEVICE = "no HIP device visible; libzkgpu has no CPU fallback";
-struct BodyOut { zk_block_record *recs; uint8_t *rec_froms; int32_t *rec_of; uint8_t *txhash, *froms, *code, *status; };
 // every output as a failure leaves it: nothing is written through a null pointer or for a negative count
 void bodies_zero(int n, const BodyOut &o) {
   if (n <= 0) return;
@@ -37,31 +22,17 @@ void bodies_zero(int n, const BodyOut &o) {
   if (o.code) memset(o.code, 0, (size_t)n);
   if (o.status) memset(o.status, 0, (size_t)n);
 }
-// zkTxSenders' refusals (capi_txs.cpp: txs_args_ok), and the three arrays of the records
+// zkTxSenders' refusals, and the three arrays of the records
 bool bodies_args_ok(const uint8_t *txs, const uint64_t *off, int n, int signer, uint64_t chain_id, const BodyOut &o) {
-  if (n < 0) { zkgpu_set_error("bodies: a negative count"); return false; }
-  if (n && (!txs || !off || !o.froms || !o.code || !o.status || !o.recs || !o.rec_froms || !o.rec_of)) { zkgpu_set_error("bodies: a null pointer"); return false; }
-  if (signer != ZK_SIGNER_FRONTIER && signer != ZK_SIGNER_HOMESTEAD && signer != ZK_SIGNER_EIP155) { zkgpu_set_error("bodies: an unknown signer"); return false; }
-  if (chain_id >> 62) { zkgpu_set_error("bodies: a chain id of 2^62 or more"); return false; }
-  for (int i = 0; i < n; i++) if (off[i + 1] < off[i]) { zkgpu_set_error("bodies: offsets decrease"); return false; }
-  return true;
+  return txs_args_ok("bodies", txs, off, n, signer, chain_id, o.froms && o.code && o.status && o.recs && o.rec_froms && o.rec_of);
 }
-// the device part under the device mutex: m, or ZKGPU_ERR_NO_DEVICE / ZKGPU_ERR_RUNTIME with every output zeroed.  roots (may be null): the transaction trie roots of
-// the n_blocks blocks between the borders, and defined, on the same upload; zeroed by the caller on an error.  n = 0 with roots: every block is empty, the trie's
-// finish launch alone.
-int bodies_run(const uint8_t *txs, const uint64_t *off, int n, int signer, uint64_t chain_id, const BodyOut &o, size_t *first_bad, const int *borders, size_t n_borders, int *rec_borders,
-               uint8_t *roots = nullptr, uint8_t *defined = nullptr) {
-  int rc;
-  try {
-    if (!gpu_available()) { zkgpu_set_error(NO_DEVICE); rc = ZKGPU_ERR_NO_DEVICE; }
-    else { std::lock_guard<std::mutex> lk(g_gpu_mutex);
-      if (roots && !n) { trie_roots(txs, off, 0, borders, n_borders - 1, true, roots, defined); rc = 0; }
-      else rc = (int)tx_records(txs, off, (size_t)n, signer, chain_id, (uint8_t *)o.recs, o.rec_froms, o.rec_of, o.txhash, o.froms, o.code, o.status, first_bad, borders, n_borders, rec_borders,
-                                roots ? borders : nullptr, roots ? n_borders - 1 : 0, roots, defined); }
-  }
-  catch (const std::exception &e) { zkgpu_set_error(e.what()); rc = ZKGPU_ERR_RUNTIME; }
-  catch (...) { zkgpu_set_error("unknown error"); rc = ZKGPU_ERR_RUNTIME; }
-  if (rc < 0) bodies_zero(n, o);                                                                    // a step failed midway: nothing half-written stays
+// the device part under the device mutex: m, or ZKGPU_ERR_NO_DEVICE / ZKGPU_ERR_RUNTIME with every output zeroed.  rq (may be null): the transaction trie roots of the
+// blocks between the borders, and defined, on the same upload; zeroed by the caller on an error.  n = 0 with rq: every block is empty, the trie's finish launch alone.
+int bodies_run(const TxsIn &in, const BodyOut &o, size_t *first_bad, const int *borders, size_t n_borders, int *rec_borders, const RootsRequest *rq = nullptr) {
+  const int rc = guarded_device([&] {
+    if (rq && !in.n) { trie_roots(in.txs, in.off, 0, *rq, true); return 0; }
+    return (int)tx_records(in, o, first_bad, borders, n_borders, rec_borders, rq); });
+  if (rc < 0) bodies_zero((int)in.n, o);                                                            // a step failed midway: nothing half-written stays
   return rc;
 }
 }  // namespace
@@ -72,7 +43,7 @@ int zkgpu_tx_records(const uint8_t *txs, const uint64_t *off, int n, int signer,
   const BodyOut o = {recs, rec_froms, rec_of, txhash, froms, code, status};
   if (!bodies_args_ok(txs, off, n, signer, chain_id, o)) { bodies_zero(n, o); return ZKGPU_ERR_ARG; }   // (before the device is asked for)
   if (n == 0) return 0;
-  return bodies_run(txs, off, n, signer, chain_id, o, nullptr, nullptr, 0, nullptr);
+  return bodies_run(TxsIn{txs, off, (size_t)n, signer, chain_id}, o, nullptr, nullptr, 0, nullptr);
 }
 int zkTxRecords(const uint8_t *txs, const uint64_t *off, int n, int signer, uint64_t chain_id, zk_block_record *recs, uint8_t (*rec_froms)[20], int32_t *rec_of, uint8_t (*txhash)[32],
                 uint8_t (*froms)[20], uint8_t *code, uint8_t *status) {
@@ -117,7 +88,8 @@ static int chain_bodies(const char *name, bool with_roots, zk_proof_cache *cache
     // 1. zkTxRecords on all n transactions; the records before each block border from the prefix values the device left
     std::vector<int> rec_first((size_t)n_blocks + 1, 0); size_t first_bad = 0; int m = 0;
     //    (with the roots: DeriveSha of every block on the same upload, a block of no transactions included)
-    if (n || (with_roots && n_blocks)) { m = bodies_run(txs, off, n, signer, chain_id, o, &first_bad, block_first, (size_t)n_blocks + 1, rec_first.data(), with_roots ? (uint8_t *)roots : nullptr, root_ok);
+    const RootsRequest rq = {block_first, (size_t)n_blocks, (uint8_t *)roots, root_ok};
+    if (n || (with_roots && n_blocks)) { m = bodies_run(TxsIn{txs, off, (size_t)n, signer, chain_id}, o, &first_bad, block_first, (size_t)n_blocks + 1, rec_first.data(), with_roots ? &rq : nullptr);
       if (m < 0) return fail(zkgpu_last_error()); }
     // 2. B0: the first block that holds a transaction with status != ZK_TX_OK — or, with the roots, whose root is undefined or is not the header's (root_ok holds
     //    "defined" here and "defined and equal" from here on)

@@ -3,21 +3,11 @@
 // boundary.
 #include <cstdio>
 #include <cstring>
-#include <mutex>
-#include <string>
-#include "../../include/zkgpu.h"
 #include "../../include/zk_tx_roots.h"
-#include "gpu.hpp"
-
-extern std::mutex g_gpu_mutex;
-extern void zkgpu_set_error(const std::string &s);
-namespace zk {
-size_t trie_roots(const uint8_t *vals, const uint64_t *off, size_t n, const int *first, size_t n_lists, bool want_tx, uint8_t *roots, uint8_t *defined);
-}
+#include "txs_host.hpp"
 using namespace zk;
 
 namespace {
-const char *const NO_DEVICE = "no HIP device visible; libzkgpu has no CPU fallback";
 // every output as a failure leaves it: nothing is written through a null pointer or for a negative count
 void roots_zero(int n_lists, uint8_t *roots, uint8_t *defined) {
   if (n_lists <= 0) return;
@@ -40,13 +30,7 @@ bool roots_args_ok(const uint8_t *vals, const uint64_t *off, int n, const int *f
 }
 // the device part under the device mutex: the number of defined roots, or ZKGPU_ERR_NO_DEVICE / ZKGPU_ERR_RUNTIME with both outputs zeroed
 int roots_run(const uint8_t *vals, const uint64_t *off, int n, const int *first, int n_lists, bool want_tx, uint8_t *roots, uint8_t *defined) {
-  int rc;
-  try {
-    if (!gpu_available()) { zkgpu_set_error(NO_DEVICE); rc = ZKGPU_ERR_NO_DEVICE; }
-    else { std::lock_guard<std::mutex> lk(g_gpu_mutex); rc = (int)trie_roots(vals, off, (size_t)n, first, (size_t)n_lists, want_tx, roots, defined); }
-  }
-  catch (const std::exception &e) { zkgpu_set_error(e.what()); rc = ZKGPU_ERR_RUNTIME; }
-  catch (...) { zkgpu_set_error("unknown error"); rc = ZKGPU_ERR_RUNTIME; }
+  const int rc = guarded_device([&] { return (int)trie_roots(vals, off, (size_t)n, RootsRequest{first, (size_t)n_lists, roots, defined}, want_tx); });
   if (rc < 0) roots_zero(n_lists, roots, defined);                                                  // a step failed midway: nothing half-written stays
   return rc;
 }

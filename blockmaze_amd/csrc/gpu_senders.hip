@@ -17,6 +17,7 @@
 #include <string>
 #include "gpu_internal.hpp"
 #include "secp256k1.cuh"
+#include "txs_host.hpp"
 
 namespace zk {
 using namespace secp;
@@ -161,6 +162,7 @@ __global__ void __launch_bounds__(SP_THREADS) k_secp_op(int op, const uint32_t *
 
 // ---- the host side ------------------------------------------------------------------------------------------------------------------------------------------------
 namespace {
+static_assert(TXL_SP_HEAD == SP_HEAD, "txs_layout.hpp carves the output of these kernels");
 struct Senders : PinnedStage {                       // one a process, every member under the device mutex
   DevBuf<uint32_t> gtab, work, io; size_t stride = 0; bool table_built = false;
   uint64_t counters[4] = {0, 0, 0, 0};
@@ -175,12 +177,12 @@ struct Senders : PinnedStage {                       // one a process, every mem
   }
   // rtable, walk, affine, address on lanes whose R, u1, u2 and flag are in the workspace; out: the head | ok n bytes (padded to words) | froms 5n | pubs 16n
   void tail(size_t n, const Ws &W, uint32_t *out, bool want_pubs, hipStream_t s) {
-    const dim3 grid(cdiv(n, SP_THREADS)), block(SP_THREADS); const uint32_t nn = (uint32_t)n; const size_t okw = (n + 3) / 4;
+    const dim3 grid(cdiv(n, SP_THREADS)), block(SP_THREADS); const uint32_t nn = (uint32_t)n; const SendersOut o = senders_out(n, want_pubs);
     HIP_CHECK(hipMemsetAsync(out, 0, 4 * SP_HEAD, s));
     hipLaunchKernelGGL(k_secp_rtable, grid, block, 0, s, nn, W);
     hipLaunchKernelGGL(k_secp_walk, grid, block, 0, s, nn, W, (const uint32_t *)gtab.get(), out);
     hipLaunchKernelGGL(k_secp_affine, grid, block, 0, s, nn, W);
-    hipLaunchKernelGGL(k_secp_address, grid, block, 0, s, nn, W, (uint8_t *)(out + SP_HEAD), out + SP_HEAD + okw, want_pubs ? out + SP_HEAD + okw + 5 * n : (uint32_t *)nullptr);
+    hipLaunchKernelGGL(k_secp_address, grid, block, 0, s, nn, W, (uint8_t *)(out + o.ok), out + o.froms, want_pubs ? out + o.pubs : (uint32_t *)nullptr);
     HIP_CHECK(hipGetLastError());
   }
   // the recovery on records that lie on the device: hash 8 words a record, R || S 16 words, V one byte; lift, scalars, then the tail.  Queues only.
@@ -202,7 +204,7 @@ size_t recover_senders(const uint8_t *sighash, const uint8_t *sigs, size_t n, bo
   if (n > 0x7FFFFFFFu) throw GpuError("senders: more than 2^31 - 1 records");
   LaneScope lane(0); hipStream_t s = gpu().stream; Senders &d = senders();                          // (the C entry holds the device mutex, as for every routine below)
   // up, in words: hash 8n | r, s 16n | v n bytes.  Down: head | ok | froms | pubs.
-  const size_t okw = (n + 3) / 4, up = 24 * n + okw, down = SP_HEAD + okw + 5 * n + (pubs ? 16 * n : 0);
+  const SendersOut o = senders_out(n, pubs != nullptr); const size_t okw = Carve::bytes(n), up = 24 * n + okw, down = o.end;
   d.pinned(4 * (up + down)); uint8_t *const pu = d.pin, *const back = d.pin + 4 * up;
   memcpy(pu, sighash, 32 * n); uint8_t *prs = pu + 32 * n, *pv = pu + 96 * n; memset(pv, 0, 4 * okw);
   for (size_t i = 0; i < n; i++) { memcpy(prs + 64 * i, sigs + 65 * i, 64); pv[i] = sigs[65 * i + 64]; }
@@ -212,14 +214,14 @@ size_t recover_senders(const uint8_t *sighash, const uint8_t *sigs, size_t n, bo
   d.body(n, in, in + 8 * n, (const uint8_t *)(in + 24 * n), homestead, W, out, pubs != nullptr, s);
   HIP_CHECK(hipMemcpyAsync(back, out, 4 * down, hipMemcpyDeviceToHost, s)); HIP_CHECK(hipStreamSynchronize(s));
   d.keep_counters(back);
-  const uint8_t *bok = back + 4 * SP_HEAD; memcpy(ok, bok, n); memcpy(froms, bok + 4 * okw, 20 * n); if (pubs) memcpy(pubs, bok + 4 * okw + 20 * n, 64 * n);
+  memcpy(ok, back + 4 * o.ok, n); memcpy(froms, back + 4 * o.froms, 20 * n); if (pubs) memcpy(pubs, back + 4 * o.pubs, 64 * n);
   size_t good = 0; for (size_t i = 0; i < n; i++) good += ok[i] != 0;
   return good;
 }
 // The same six launches on records another routine left on the device (gpu_txs.hip): hash n x 8 words, rs n x 16 words, v n bytes, all big-endian bytes in memory
 // order.  out: recover_senders_out_words(n) words: the head | ok n bytes (padded to words) | froms 5n.  Queues on s and returns; the caller holds the device mutex,
 // synchronises, and hands the head to senders_keep_head.
-size_t recover_senders_out_words(size_t n) { return SP_HEAD + (n + 3) / 4 + 5 * n; }
+size_t recover_senders_out_words(size_t n) { return senders_out(n, false).end; }
 void recover_senders_queue(const uint32_t *hash, const uint32_t *rs, const uint8_t *v, size_t n, bool homestead, uint32_t *out, hipStream_t s) {
   if (!n) return;
   if (n > 0x7FFFFFFFu) throw GpuError("senders: more than 2^31 - 1 records");
@@ -232,7 +234,7 @@ void probe_secp_lincomb(const uint8_t *u1, const uint8_t *u2, const uint8_t *px,
   if (!u1 || !u2 || !px || !py || !out_xy || !out_inf) throw GpuError("probe_secp_lincomb: a null pointer");
   if (n > (1u << 24)) throw GpuError("probe_secp_lincomb: more than 2^24 lanes");
   LaneScope lane(0); hipStream_t s = gpu().stream; Senders &d = senders();                          // (the C entry holds the device mutex)
-  const size_t okw = (n + 3) / 4, up = 32 * n, down = SP_HEAD + okw + 5 * n + 16 * n;
+  const SendersOut o = senders_out(n, true); const size_t up = 32 * n, down = o.end;
   d.pinned(4 * (up + down)); uint8_t *const back = d.pin + 4 * up;
   memcpy(d.pin, u1, 32 * n); memcpy(d.pin + 32 * n, u2, 32 * n); memcpy(d.pin + 64 * n, px, 32 * n); memcpy(d.pin + 96 * n, py, 32 * n);
   grow_buf(d.io, up + down); uint32_t *in = d.io.get(), *out = in + up;
@@ -242,8 +244,8 @@ void probe_secp_lincomb(const uint8_t *u1, const uint8_t *u2, const uint8_t *px,
   d.tail(n, W, out, true, s);
   HIP_CHECK(hipMemcpyAsync(back, out, 4 * down, hipMemcpyDeviceToHost, s)); HIP_CHECK(hipStreamSynchronize(s));
   d.keep_counters(back);
-  const uint8_t *bok = back + 4 * SP_HEAD; for (size_t i = 0; i < n; i++) out_inf[i] = bok[i] ? 0 : 1;
-  memcpy(out_xy, bok + 4 * okw + 20 * n, 64 * n);
+  const uint8_t *bok = back + 4 * o.ok; for (size_t i = 0; i < n; i++) out_inf[i] = bok[i] ? 0 : 1;
+  memcpy(out_xy, back + 4 * o.pubs, 64 * n);
 }
 void probe_secp_ops(int op, const uint8_t *a, const uint8_t *b, size_t n, uint8_t *out) {
   if (op < 0 || op >= SO_OPS) throw GpuError("probe_secp_ops: unknown operation");

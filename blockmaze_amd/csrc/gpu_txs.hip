@@ -25,12 +25,9 @@
 #include <string>
 #include "gpu_internal.hpp"
 #include "secp256k1.cuh"
+#include "txs_host.hpp"
 
 namespace zk {
-size_t recover_senders_out_words(size_t n);
-void recover_senders_queue(const uint32_t *hash, const uint32_t *rs, const uint8_t *v, size_t n, bool homestead, uint32_t *out, hipStream_t s);
-void senders_keep_head(const uint32_t *head);
-
 constexpr int TX_THREADS = 128;
 enum { TX_OK = 0, TX_MALFORMED = 1, TX_CHAIN_ID = 2, TX_SIG = 3, TX_DEPOSIT_KEY = 4 };
 enum { SIGNER_FRONTIER = 0, SIGNER_HOMESTEAD = 1, SIGNER_EIP155 = 2 };
@@ -589,155 +586,137 @@ struct Txs : PinnedStage {                           // one a process, every mem
   void grow(size_t words) { if (io.size() >= words) return; const size_t want = std::max(words, 2 * io.size()); io = DevBuf<uint32_t>(); io = DevBuf<uint32_t>(want); }   // (a failed growth leaves no workspace)
 };
 Txs &txs_state() { static Txs *t = new Txs; return *t; }   // (never destroyed: the runtime may be gone when statics are)
-size_t up8(size_t v) { return (v + 7) / 8 * 8; }
-// pinned: the bytes off[0] .. off[n) of the caller's buffer, padded to 8, then off itself, then (the trie roots) the n_first entries of first as 32-bit words, padded
-// to 8; returns the bytes staged
-size_t stage(Txs &d, const uint8_t *bytes, const uint64_t *off, size_t n, size_t down_bytes, uint8_t **back, const int *first = nullptr, size_t n_first = 0) {
-  const size_t total = (size_t)(off[n] - off[0]), up0 = up8(total) + 8 * (n + 1), up = up0 + up8(4 * n_first);
-  d.pinned(up + down_bytes); if (total) memcpy(d.pin, bytes + off[0], total); memset(d.pin + total, 0, up8(total) - total); memcpy(d.pin + up8(total), off, 8 * (n + 1));
-  if (n_first) { memcpy(d.pin + up0, first, 4 * n_first); memset(d.pin + up0 + 4 * n_first, 0, up8(4 * n_first) - 4 * n_first); }   // (checked by the caller: 0 .. n, so int and uint32_t agree)
-  *back = d.pin + up; return up;
+static_assert(TXL_D_WORDS == TD_WORDS && TXL_E_WORDS == TE_WORDS && TXL_HEAD_WORDS == BH_WORDS && TXL_REC_WORDS == REC_WORDS && TXL_THREADS == TX_THREADS, "txs_layout.hpp carves for these kernels");
+// pinned, on a layout of txs_layout.hpp: the upload's three pieces — the bytes off[0] .. off[n) of the caller's buffer, padded to 8, off itself, the n_first entries of
+// first (checked by the caller: 0 .. n, so int and uint32_t agree), padded to 8; returns where the download will land
+uint8_t *stage(Txs &d, const TxsUpload &L, const uint8_t *bytes, const uint64_t *off, size_t n, const int *first) {
+  d.pinned(L.pin_bytes); uint8_t *const back = d.pin + L.up, *const f = d.pin + 4 * L.first;
+  if (L.total) memcpy(d.pin, bytes + off[0], L.total);
+  memset(d.pin + L.total, 0, L.total8 - L.total); memcpy(d.pin + L.total8, off, 8 * (n + 1));
+  if (L.n_first) { memcpy(f, first, 4 * L.n_first); memset(f + 4 * L.n_first, 0, back - (f + 4 * L.n_first)); }
+  return back;
 }
+// The prologue of every call here: the upload staged, the workspace grown to the layout and its slack, the upload queued on s.  dev(x): region x on the device;
+// host(x): where region x lies once L.down .. L.down_end has come down to `back`.
+struct Staged {
+  const TxsUpload &L; uint32_t *p; uint8_t *back; const uint8_t *dtx; const uint64_t *doff; const uint32_t *dfirst;
+  SyncAtExit sync;                                                                                  // (also where staging or growing fails: the stream is idle then)
+  Staged(const TxsUpload &L, const uint8_t *bytes, const uint64_t *off, size_t n, const int *first, hipStream_t s) : L(L) {
+    Txs &d = txs_state(); back = stage(d, L, bytes, off, n, first);
+    d.grow(L.end + TXL_SLACK); p = d.io.get(); if (!p) throw GpuError("txs: no workspace");
+    dtx = (const uint8_t *)p; doff = (const uint64_t *)(p + L.off); dfirst = p + L.first;
+    HIP_CHECK(hipMemcpyAsync(p, d.pin, L.up, hipMemcpyHostToDevice, s));
+  }
+  uint32_t *dev(size_t x) const { return p + x; }
+  uint8_t *host(size_t x) const { return back + 4 * (x - L.down); }
+};
 // The launches behind the upload: a leaf a value, a level for every nibble depth of the longest key — it depends on the largest list alone —, a root a list.  D: the
-// walk's descriptor (the transaction forms, with bad, n_lists words, and defined) or null.  node: 8 n words at an 8-byte boundary, roots: 8 n_lists words likewise.
-void trie_queue(const uint8_t *dvals, const uint64_t *doff, size_t n, const uint32_t *dfirst, size_t n_lists, size_t largest, const uint32_t *D, uint32_t *blk_of, uint32_t *bad, uint32_t *node,
-                uint32_t *roots, uint8_t *defined, hipStream_t s) {
-  const dim3 block(TX_THREADS);
+// walk's descriptor (the transaction forms: bad and defined are written) or null.
+void trie_queue(const Staged &g, size_t n, size_t n_lists, size_t largest, const uint32_t *D, const TrieWords &w, hipStream_t s) {
+  const dim3 block(TX_THREADS); uint32_t *blk_of = g.dev(w.blk_of), *bad = g.dev(w.bad); uint64_t *node = (uint64_t *)g.dev(w.node);
   if (D) HIP_CHECK(hipMemsetAsync(bad, 0, 4 * n_lists, s));
   if (n) {
-    if (D) hipLaunchKernelGGL(k_trie_leaf<true>, dim3(cdiv(n, TX_THREADS)), block, 0, s, dvals, doff, (uint32_t)n, dfirst, (uint32_t)n_lists, D, blk_of, bad, (uint64_t *)node);
-    else hipLaunchKernelGGL(k_trie_leaf<false>, dim3(cdiv(n, TX_THREADS)), block, 0, s, dvals, doff, (uint32_t)n, dfirst, (uint32_t)n_lists, (const uint32_t *)nullptr, blk_of, (uint32_t *)nullptr, (uint64_t *)node);
+    if (D) hipLaunchKernelGGL(k_trie_leaf<true>, dim3(cdiv(n, TX_THREADS)), block, 0, s, g.dtx, g.doff, (uint32_t)n, g.dfirst, (uint32_t)n_lists, D, blk_of, bad, node);
+    else hipLaunchKernelGGL(k_trie_leaf<false>, dim3(cdiv(n, TX_THREADS)), block, 0, s, g.dtx, g.doff, (uint32_t)n, g.dfirst, (uint32_t)n_lists, (const uint32_t *)nullptr, blk_of, (uint32_t *)nullptr, node);
     const int nibbles = largest <= 1 ? 0 : largest <= 0x80 ? 2 : largest <= 0x100 ? 4 : largest <= 0x10000 ? 6 : largest <= 0x1000000 ? 8 : 10;   // of rlp(largest - 1); one value: no branch
-    for (int depth = nibbles - 1; depth >= 0; depth--) hipLaunchKernelGGL(k_trie_level, dim3(cdiv(n, TX_THREADS)), block, 0, s, (uint32_t)n, (uint32_t)depth, dfirst, (const uint32_t *)blk_of, (uint64_t *)node);
+    for (int depth = nibbles - 1; depth >= 0; depth--) hipLaunchKernelGGL(k_trie_level, dim3(cdiv(n, TX_THREADS)), block, 0, s, (uint32_t)n, (uint32_t)depth, g.dfirst, (const uint32_t *)blk_of, node);
   }
-  hipLaunchKernelGGL(k_trie_finish, dim3(cdiv(n_lists, TX_THREADS)), block, 0, s, (uint32_t)n_lists, dfirst, (const uint64_t *)node, D ? (const uint32_t *)bad : (const uint32_t *)nullptr, (uint64_t *)roots, defined);
+  hipLaunchKernelGGL(k_trie_finish, dim3(cdiv(n_lists, TX_THREADS)), block, 0, s, (uint32_t)n_lists, g.dfirst, (const uint64_t *)node, D ? (const uint32_t *)bad : (const uint32_t *)nullptr,
+                     (uint64_t *)g.dev(w.roots), D ? (uint8_t *)g.dev(w.defined) : (uint8_t *)nullptr);
   HIP_CHECK(hipGetLastError());
 }
 size_t largest_list(const int *first, size_t n_lists) { size_t m = 0; for (size_t b = 0; b < n_lists; b++) m = std::max(m, (size_t)(first[b + 1] - first[b])); return m; }
-// device words behind a base for the trie's own arrays: blk_of n | bad n_lists | (to 8 bytes) | node 8n | roots 8 n_lists | defined, n_lists bytes (to 8 bytes)
-struct TrieWords { size_t blk_of, bad, node, roots, defined, end; };
-TrieWords trie_words(size_t base, size_t n, size_t n_lists) {
-  TrieWords w; w.blk_of = base; w.bad = w.blk_of + n; w.node = (w.bad + n_lists + 1) / 2 * 2; w.roots = w.node + 8 * n; w.defined = w.roots + 8 * n_lists; w.end = w.defined + (n_lists + 7) / 8 * 2; return w;
-}
 }  // namespace
 
 // zkgpu_list_trie_roots (want_tx false: the values verbatim) and zkgpu_tx_roots (want_tx: the walk first; defined is written).  The caller has checked the arguments
 // and holds the device mutex; n_lists > 0.  One upload (the bytes, off, first), one download (roots, then defined).  Returns the number of roots that are defined.
-size_t trie_roots(const uint8_t *vals, const uint64_t *off, size_t n, const int *first, size_t n_lists, bool want_tx, uint8_t *roots, uint8_t *defined) {
+size_t trie_roots(const uint8_t *vals, const uint64_t *off, size_t n, const RootsRequest &rq, bool want_tx) {
+  const size_t n_lists = rq.n_lists;
   if (n > 0x3FFFFFFFu || n_lists > 0x3FFFFFFFu) throw GpuError("trie roots: more than 2^30 - 1 values or lists");
-  LaneScope lane(0); hipStream_t s = gpu().stream; Txs &d = txs_state(); uint8_t *back = nullptr;
-  const size_t down = 32 * n_lists + up8(n_lists), up = stage(d, vals, off, n, down, &back, first, n_lists + 1), total8 = up - 8 * (n + 1) - up8(4 * (n_lists + 1));
-  // device, in words: up | (the walk: D | rs 16n | v) | the trie's arrays
-  const size_t okw = (n + 3) / 4, w_walk = want_tx ? (TD_WORDS * n + 16 * n + okw + 1) / 2 * 2 : 0; const TrieWords w = trie_words(up / 4 + w_walk, n, n_lists);
-  d.grow(w.end + 2); uint32_t *p = d.io.get(); if (!p) throw GpuError("txs: no workspace");
-  const uint8_t *dvals = (const uint8_t *)p; const uint64_t *doff = (const uint64_t *)((const uint8_t *)p + total8); const uint32_t *dfirst = (const uint32_t *)(doff + n + 1);
-  uint32_t *D = p + up / 4, *rs = D + TD_WORDS * n, *v = rs + 16 * n;
-  SyncAtExit sync;
-  HIP_CHECK(hipMemcpyAsync(p, d.pin, up, hipMemcpyHostToDevice, s));
-  if (want_tx && n) hipLaunchKernelGGL(k_tx_walk<false>, dim3(cdiv(n, TX_THREADS)), dim3(TX_THREADS), 0, s, dvals, doff, (uint32_t)n, (int)SIGNER_FRONTIER, (uint64_t)0, D, (uint8_t *)rs, (uint8_t *)v,
-                                       (uint8_t *)nullptr, (uint32_t *)nullptr, (uint8_t *)nullptr, (uint32_t *)nullptr);   // (MALFORMED and the 0xC0 position depend on no signer)
-  trie_queue(dvals, doff, n, dfirst, n_lists, largest_list(first, n_lists), want_tx ? (const uint32_t *)D : (const uint32_t *)nullptr, p + w.blk_of, p + w.bad, p + w.node, p + w.roots,
-             want_tx ? (uint8_t *)(p + w.defined) : (uint8_t *)nullptr, s);
-  HIP_CHECK(hipMemcpyAsync(back, p + w.roots, want_tx ? down : 32 * n_lists, hipMemcpyDeviceToHost, s)); HIP_CHECK(hipStreamSynchronize(s));
-  memcpy(roots, back, 32 * n_lists); size_t good = n_lists;
-  if (want_tx) { memcpy(defined, back + 32 * n_lists, n_lists); good = 0; for (size_t b = 0; b < n_lists; b++) good += defined[b] != 0; }
+  LaneScope lane(0); hipStream_t s = gpu().stream; const TrieRootsLayout L = trie_roots_layout(n, (size_t)(off[n] - off[0]), n_lists, want_tx);
+  const Staged g(L, vals, off, n, rq.first, s); uint32_t *D = g.dev(L.D);
+  if (want_tx && n) hipLaunchKernelGGL(k_tx_walk<false>, dim3(cdiv(n, TX_THREADS)), dim3(TX_THREADS), 0, s, g.dtx, g.doff, (uint32_t)n, (int)SIGNER_FRONTIER, (uint64_t)0, D, (uint8_t *)g.dev(L.rs),
+                                       (uint8_t *)g.dev(L.v), (uint8_t *)nullptr, (uint32_t *)nullptr, (uint8_t *)nullptr, (uint32_t *)nullptr);   // (MALFORMED and the 0xC0 position depend on no signer)
+  trie_queue(g, n, n_lists, largest_list(rq.first, n_lists), want_tx ? (const uint32_t *)D : (const uint32_t *)nullptr, L.trie, s);
+  HIP_CHECK(hipMemcpyAsync(g.back, g.dev(L.down), 4 * (L.down_end - L.down), hipMemcpyDeviceToHost, s)); HIP_CHECK(hipStreamSynchronize(s));
+  memcpy(rq.roots, g.host(L.trie.roots), 32 * n_lists); size_t good = n_lists;
+  if (want_tx) { memcpy(rq.defined, g.host(L.trie.defined), n_lists); good = 0; for (size_t b = 0; b < n_lists; b++) good += rq.defined[b] != 0; }
   return good;
 }
 
 // The caller has checked the arguments and holds the device mutex.  want_senders: zkTxSenders (sighash, sigs, deposit_from null), else zkTxSigningInputs.
 // One upload (txs, then off), three launches — nine with the recovery — and one download.  Returns the number of records with status OK.
-size_t tx_sender_inputs(const uint8_t *txs, const uint64_t *off, size_t n, int signer, uint64_t chain_id, bool want_senders, uint8_t *txhash, uint8_t *sighash, uint8_t *sigs,
-                        uint8_t *froms /* deposit_from or froms; may be null for deposit_from */, uint8_t *code, uint8_t *status) {
+size_t tx_sender_inputs(const TxsIn &in, bool want_senders, const SenderInputsOut &o) {
+  const size_t n = in.n;
   if (!n) return 0;
   if (n > 0x3FFFFFFFu) throw GpuError("txs: more than 2^30 - 1 transactions");
-  LaneScope lane(0); hipStream_t s = gpu().stream; Txs &d = txs_state();
-  // down, in words: txhash 8n | sighash 8n | froms 5n | then bytes: sigs 65n | status n | code n | the recovery's head, 4 words
-  const size_t okw = (n + 3) / 4, down_words = 21 * n + (65 * n + 3) / 4 + 2 * okw + 4, down = 4 * down_words; uint8_t *back = nullptr;
-  const size_t up = stage(d, txs, off, n, down, &back), total8 = up - 8 * (n + 1);
-  // device, in words: up | D | hash 8n | rs 16n | v | the recovery's out | down
-  const size_t w_up = up / 4, w_D = TD_WORDS * n, w_rec = recover_senders_out_words(n), words = w_up + w_D + 24 * n + okw + w_rec + down_words + 2;
-  d.grow(words); uint32_t *p = d.io.get(); if (!p) throw GpuError("txs: no workspace");
-  const uint8_t *dtx = (const uint8_t *)p; const uint64_t *doff = (const uint64_t *)((const uint8_t *)p + total8);
-  uint32_t *D = p + w_up, *hash = D + w_D, *rs = hash + 8 * n, *v = rs + 16 * n, *rec = v + okw, *dn = rec + w_rec;
-  uint32_t *d_txhash = dn, *d_sighash = dn + 8 * n, *d_froms = dn + 16 * n; uint8_t *d_sigs = (uint8_t *)(dn + 21 * n), *d_status = d_sigs + 4 * ((65 * n + 3) / 4), *d_code = d_status + 4 * okw; uint32_t *d_head = dn + down_words - 4;
-  SyncAtExit sync;
-  HIP_CHECK(hipMemcpyAsync(p, d.pin, up, hipMemcpyHostToDevice, s));
+  LaneScope lane(0); hipStream_t s = gpu().stream; const SenderInputsLayout L = sender_inputs_layout(n, (size_t)(in.off[n] - in.off[0]));
+  const Staged g(L, in.txs, in.off, n, nullptr, s);
+  uint32_t *D = g.dev(L.D), *hash = g.dev(L.hash), *rs = g.dev(L.rs), *v = g.dev(L.v), *rec = g.dev(L.rec);
   const dim3 block(TX_THREADS), grid(cdiv(n, TX_THREADS)), grid2(cdiv(2 * n, TX_THREADS));
-  hipLaunchKernelGGL(k_tx_walk<false>, grid, block, 0, s, dtx, doff, (uint32_t)n, signer, chain_id, D, (uint8_t *)rs, (uint8_t *)v, want_senders ? (uint8_t *)nullptr : d_sigs,
+  hipLaunchKernelGGL(k_tx_walk<false>, grid, block, 0, s, g.dtx, g.doff, (uint32_t)n, in.signer, in.chain_id, D, (uint8_t *)rs, (uint8_t *)v, want_senders ? (uint8_t *)nullptr : (uint8_t *)g.dev(L.sigs),
                      (uint32_t *)nullptr, (uint8_t *)nullptr, (uint32_t *)nullptr);
-  hipLaunchKernelGGL(k_tx_hash, grid2, block, 0, s, dtx, doff, (uint32_t)n, chain_id, (const uint32_t *)D, want_senders ? hash : d_sighash, d_txhash);
+  hipLaunchKernelGGL(k_tx_hash, grid2, block, 0, s, g.dtx, g.doff, (uint32_t)n, in.chain_id, (const uint32_t *)D, want_senders ? hash : g.dev(L.sighash), g.dev(L.txhash));
   HIP_CHECK(hipGetLastError());
-  if (want_senders) recover_senders_queue(hash, rs, (const uint8_t *)v, n, signer != SIGNER_FRONTIER, rec, s);
-  hipLaunchKernelGGL(k_tx_finish, grid, block, 0, s, (uint32_t)n, (const uint32_t *)D, want_senders ? (const uint8_t *)(rec + 4) : (const uint8_t *)nullptr,
-                     (const uint32_t *)(rec + 4 + okw), d_froms, d_status, d_code, want_senders ? (const uint32_t *)rec : (const uint32_t *)nullptr, d_head);
+  if (want_senders) recover_senders_queue(hash, rs, (const uint8_t *)v, n, in.signer != SIGNER_FRONTIER, rec, s);
+  hipLaunchKernelGGL(k_tx_finish, grid, block, 0, s, (uint32_t)n, (const uint32_t *)D, want_senders ? (const uint8_t *)g.dev(L.ok) : (const uint8_t *)nullptr, (const uint32_t *)g.dev(L.recovered),
+                     g.dev(L.froms), (uint8_t *)g.dev(L.status), (uint8_t *)g.dev(L.code), want_senders ? (const uint32_t *)rec : (const uint32_t *)nullptr, g.dev(L.head));
   HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipMemcpyAsync(back, dn, down, hipMemcpyDeviceToHost, s)); HIP_CHECK(hipStreamSynchronize(s));
-  if (want_senders) senders_keep_head((const uint32_t *)(back + down - 16));
-  if (txhash) memcpy(txhash, back, 32 * n);
-  if (sighash) memcpy(sighash, back + 32 * n, 32 * n);
-  if (froms) memcpy(froms, back + 64 * n, 20 * n);
-  if (sigs) memcpy(sigs, back + 84 * n, 65 * n);
-  const uint8_t *bst = back + 84 * n + 4 * ((65 * n + 3) / 4); memcpy(status, bst, n); memcpy(code, bst + 4 * okw, n);
-  size_t good = 0; for (size_t i = 0; i < n; i++) good += status[i] == TX_OK;
+  HIP_CHECK(hipMemcpyAsync(g.back, g.dev(L.down), 4 * (L.down_end - L.down), hipMemcpyDeviceToHost, s)); HIP_CHECK(hipStreamSynchronize(s));
+  if (want_senders) senders_keep_head((const uint32_t *)g.host(L.head));
+  if (o.txhash) memcpy(o.txhash, g.host(L.txhash), 32 * n);
+  if (o.sighash) memcpy(o.sighash, g.host(L.sighash), 32 * n);
+  if (o.froms) memcpy(o.froms, g.host(L.froms), 20 * n);
+  if (o.sigs) memcpy(o.sigs, g.host(L.sigs), 65 * n);
+  memcpy(o.status, g.host(L.status), n); memcpy(o.code, g.host(L.code), n);
+  size_t good = 0; for (size_t i = 0; i < n; i++) good += o.status[i] == TX_OK;
   return good;
 }
 // zkTxRecords (include/zk_bodies.h).  The caller has checked the arguments and holds the device mutex.  One upload (txs, then off); the walk with both descriptors, the
 // hashes, the recovery's six launches once for all lanes, k_body_finish, k_body_scan, k_body_scatter, k_body_gather; four words that say m; one download: the small
 // outputs and recs[0 .. m).  rec_froms[m .. n) is zeroed, recs[m .. n) is not written.  first_bad: the first transaction with status != OK, n where there is none.
 // borders (may be null): n_borders transaction indices in 0 .. n; rec_borders[k] = the records before transaction borders[k].  Returns m.
-// roots (may be null; verifyChainBodiesRoots): the transaction trie roots of the n_blocks blocks that block_first names, and defined, as zkTxRoots writes
-// them — block_first rides in the same upload, the trie's launches follow the hashes on the walk's descriptor, the roots come down with the records.  Without roots
-// nothing of this is queued and the launches are the ones zkTxRecords and verifyChainBodies have always made.
+// rq (may be null; verifyChainBodiesRoots): the transaction trie roots of the blocks that rq->first names, and defined, as zkTxRoots writes them —
+// first rides in the same upload, the trie's launches follow the hashes on the walk's descriptor, the roots come down with the records.  Without it nothing of this
+// is queued and the launches are the ones zkTxRecords and verifyChainBodies have always made.
 static bool g_gather_bytewise = false;                                                              // (zkgpu_test_bodies_gather: the measurement of DESIGN.md §23; under the device mutex)
 void tx_records_gather_bytewise(bool on) { g_gather_bytewise = on; }
-size_t tx_records(const uint8_t *txs, const uint64_t *off, size_t n, int signer, uint64_t chain_id, uint8_t *recs, uint8_t *rec_froms, int32_t *rec_of, uint8_t *txhash, uint8_t *froms,
-                  uint8_t *code, uint8_t *status, size_t *first_bad, const int *borders, size_t n_borders, int *rec_borders, const int *block_first, size_t n_blocks, uint8_t *roots,
-                  uint8_t *defined) {
+size_t tx_records(const TxsIn &in, const BodyOut &o, size_t *first_bad, const int *borders, size_t n_borders, int *rec_borders, const RootsRequest *rq) {
+  const size_t n = in.n, n_blocks = rq ? rq->n_lists : 0;
   if (!n) { if (first_bad) *first_bad = 0; for (size_t k = 0; k < n_borders; k++) rec_borders[k] = 0; return 0; }
   if (n > 0x3FFFFFFFu) throw GpuError("txs: more than 2^30 - 1 transactions");
-  LaneScope lane(0); hipStream_t s = gpu().stream; Txs &d = txs_state();
-  // down, in words: head 8 (first_bad, m, -, -, the recovery's four) | txhash 8n | froms 5n | rec_froms 5n | rec_of n | prefix n + 1 | status | code | (to 8 bytes) | recs 180 m
-  const size_t okw = (n + 3) / 4, nb = cdiv(n, TX_THREADS), small_words = (2 * BH_WORDS + 20 * n + 1 + 2 * okw + 1) / 2 * 2, down_words = small_words + (size_t)REC_WORDS * n; uint8_t *back = nullptr;
-  const size_t n_first = roots ? n_blocks + 1 : 0, roots_down = roots ? 32 * n_blocks + up8(n_blocks) : 0;
-  const size_t up = stage(d, txs, off, n, 4 * down_words + roots_down, &back, block_first, n_first), total8 = up - 8 * (n + 1) - up8(4 * n_first);
-  // device, in words: up | D | E | hash 8n | rs 16n | xy 16n | v | the recovery's out | src_of n | counts nb | bases nb | (to 8 bytes) | down
-  const size_t w_up = up / 4, w_D = TD_WORDS * n, w_E = TE_WORDS * n, w_rec = recover_senders_out_words(n), before = (w_up + w_D + w_E + 40 * n + okw + w_rec + n + 2 * nb + 1) / 2 * 2;
-  const TrieWords tw = trie_words((before + down_words + 1) / 2 * 2, roots ? n : 0, roots ? n_blocks : 0);   // (behind the download; nothing where no roots are asked for)
-  d.grow(tw.end + 2); uint32_t *p = d.io.get(); if (!p) throw GpuError("txs: no workspace");
-  const uint8_t *dtx = (const uint8_t *)p; const uint64_t *doff = (const uint64_t *)((const uint8_t *)p + total8);
-  uint32_t *D = p + w_up, *E = D + w_D, *hash = E + w_E, *rs = hash + 8 * n, *xy = rs + 16 * n, *v = xy + 16 * n, *rec = v + okw, *src_of = rec + w_rec, *counts = src_of + n, *bases = counts + nb, *dn = p + before;
-  uint32_t *d_head = dn, *d_txhash = dn + 2 * BH_WORDS, *d_froms = d_txhash + 8 * n, *d_rec_froms = d_froms + 5 * n, *d_rec_of = d_rec_froms + 5 * n, *d_prefix = d_rec_of + n;
-  uint8_t *d_status = (uint8_t *)(d_prefix + n + 1), *d_code = d_status + 4 * okw; uint32_t *d_recs = dn + small_words;      // (8-byte aligned: `before` and small_words are even)
-  SyncAtExit sync;
-  HIP_CHECK(hipMemcpyAsync(p, d.pin, up, hipMemcpyHostToDevice, s));
-  const dim3 block(TX_THREADS), grid(nb), grid2(cdiv(2 * n, TX_THREADS));
-  hipLaunchKernelGGL(k_tx_walk<true>, grid, block, 0, s, dtx, doff, (uint32_t)n, signer, chain_id, D, (uint8_t *)rs, (uint8_t *)v, (uint8_t *)nullptr, E, (uint8_t *)xy, d_head + BH_FIRST_BAD);
-  hipLaunchKernelGGL(k_tx_hash, grid2, block, 0, s, dtx, doff, (uint32_t)n, chain_id, (const uint32_t *)D, hash, d_txhash);
+  LaneScope lane(0); hipStream_t s = gpu().stream; const RecordsLayout L = records_layout(n, (size_t)(in.off[n] - in.off[0]), n_blocks);
+  const Staged g(L, in.txs, in.off, n, rq ? rq->first : nullptr, s);
+  uint32_t *D = g.dev(L.D), *E = g.dev(L.E), *hash = g.dev(L.hash), *rs = g.dev(L.rs), *xy = g.dev(L.xy), *v = g.dev(L.v), *rec = g.dev(L.rec), *src_of = g.dev(L.src_of), *counts = g.dev(L.counts), *bases = g.dev(L.bases);
+  uint32_t *d_head = g.dev(L.head), *d_froms = g.dev(L.froms), *d_rec_froms = g.dev(L.rec_froms), *d_rec_of = g.dev(L.rec_of), *d_prefix = g.dev(L.prefix), *d_recs = g.dev(L.recs);
+  const uint32_t *recovered = g.dev(L.recovered);
+  const dim3 block(TX_THREADS), grid(cdiv(n, TX_THREADS)), grid2(cdiv(2 * n, TX_THREADS));
+  hipLaunchKernelGGL(k_tx_walk<true>, grid, block, 0, s, g.dtx, g.doff, (uint32_t)n, in.signer, in.chain_id, D, (uint8_t *)rs, (uint8_t *)v, (uint8_t *)nullptr, E, (uint8_t *)xy, d_head + BH_FIRST_BAD);
+  hipLaunchKernelGGL(k_tx_hash, grid2, block, 0, s, g.dtx, g.doff, (uint32_t)n, in.chain_id, (const uint32_t *)D, hash, g.dev(L.txhash));
   HIP_CHECK(hipGetLastError());
-  if (roots) trie_queue(dtx, doff, n, (const uint32_t *)(doff + n + 1), n_blocks, largest_list(block_first, n_blocks), (const uint32_t *)D, p + tw.blk_of, p + tw.bad, p + tw.node, p + tw.roots,
-                        (uint8_t *)(p + tw.defined), s);
-  recover_senders_queue(hash, rs, (const uint8_t *)v, n, signer != SIGNER_FRONTIER, rec, s);       // once, for every lane; a deposit's Homestead rule where the flag is 0: k_body_finish
-  hipLaunchKernelGGL(k_body_finish, grid, block, 0, s, (uint32_t)n, (int)(signer != SIGNER_FRONTIER), (const uint32_t *)D, (const uint32_t *)E, (const uint8_t *)(rec + 4), (const uint32_t *)(rec + 4 + okw),
-                     (const uint32_t *)rs, (const uint32_t *)xy, d_froms, d_status, d_code, (int32_t *)d_rec_of, counts, d_head, (const uint32_t *)rec);
-  hipLaunchKernelGGL(k_body_scan, dim3(1), dim3(BODY_SCAN_THREADS), 0, s, (const uint32_t *)counts, (uint32_t)nb, bases, d_head);
+  if (n_blocks) trie_queue(g, n, n_blocks, largest_list(rq->first, n_blocks), (const uint32_t *)D, L.trie, s);
+  recover_senders_queue(hash, rs, (const uint8_t *)v, n, in.signer != SIGNER_FRONTIER, rec, s);    // once, for every lane; a deposit's Homestead rule where the flag is 0: k_body_finish
+  hipLaunchKernelGGL(k_body_finish, grid, block, 0, s, (uint32_t)n, (int)(in.signer != SIGNER_FRONTIER), (const uint32_t *)D, (const uint32_t *)E, (const uint8_t *)g.dev(L.ok), recovered,
+                     (const uint32_t *)rs, (const uint32_t *)xy, d_froms, (uint8_t *)g.dev(L.status), (uint8_t *)g.dev(L.code), (int32_t *)d_rec_of, counts, d_head, (const uint32_t *)rec);
+  hipLaunchKernelGGL(k_body_scan, dim3(1), dim3(BODY_SCAN_THREADS), 0, s, (const uint32_t *)counts, (uint32_t)grid.x, bases, d_head);
   hipLaunchKernelGGL(k_body_scatter, grid, block, 0, s, (uint32_t)n, (const uint32_t *)bases, (const uint32_t *)d_froms, (int32_t *)d_rec_of, d_prefix, src_of, d_rec_froms);
   const dim3 gblock(BODY_GATHER_THREADS), ggrid(cdiv(64 * n, BODY_GATHER_THREADS));
-  if (g_gather_bytewise) hipLaunchKernelGGL(k_body_gather<false>, ggrid, gblock, 0, s, dtx, doff, (uint32_t)n, (const uint32_t *)D, (const uint32_t *)E, (const uint32_t *)(rec + 4 + okw), (const uint32_t *)src_of, (const uint32_t *)d_prefix, d_recs);
-  else hipLaunchKernelGGL(k_body_gather<true>, ggrid, gblock, 0, s, dtx, doff, (uint32_t)n, (const uint32_t *)D, (const uint32_t *)E, (const uint32_t *)(rec + 4 + okw), (const uint32_t *)src_of, (const uint32_t *)d_prefix, d_recs);
+  if (g_gather_bytewise) hipLaunchKernelGGL(k_body_gather<false>, ggrid, gblock, 0, s, g.dtx, g.doff, (uint32_t)n, (const uint32_t *)D, (const uint32_t *)E, recovered, (const uint32_t *)src_of, (const uint32_t *)d_prefix, d_recs);
+  else hipLaunchKernelGGL(k_body_gather<true>, ggrid, gblock, 0, s, g.dtx, g.doff, (uint32_t)n, (const uint32_t *)D, (const uint32_t *)E, recovered, (const uint32_t *)src_of, (const uint32_t *)d_prefix, d_recs);
   HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipMemcpyAsync(back, dn, 4 * BH_WORDS, hipMemcpyDeviceToHost, s)); HIP_CHECK(hipStreamSynchronize(s));   // m: the length of the download
-  uint32_t head[BH_WORDS]; memcpy(head, back, sizeof head); const size_t m = head[BH_M];
+  HIP_CHECK(hipMemcpyAsync(g.back, d_head, 4 * BH_WORDS, hipMemcpyDeviceToHost, s)); HIP_CHECK(hipStreamSynchronize(s));   // m: the length of the download
+  uint32_t head[BH_WORDS]; memcpy(head, g.back, sizeof head); const size_t m = head[BH_M];
   if (m > n || head[BH_FIRST_BAD] > n) throw GpuError("txs: the record count left by the device is out of range");
-  HIP_CHECK(hipMemcpyAsync(back, dn, 4 * (small_words + (size_t)REC_WORDS * m), hipMemcpyDeviceToHost, s));
-  if (roots) HIP_CHECK(hipMemcpyAsync(back + 4 * down_words, p + tw.roots, roots_down, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(g.back, g.dev(L.down), 4 * (L.recs - L.down + (size_t)REC_WORDS * m), hipMemcpyDeviceToHost, s));
+  uint8_t *const roots_back = g.host(L.down_end);                                                   // (the second range lands behind the whole of the first)
+  if (n_blocks) HIP_CHECK(hipMemcpyAsync(roots_back, g.dev(L.trie.roots), 4 * (L.trie.end - L.trie.roots), hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
-  if (roots) { memcpy(roots, back + 4 * down_words, 32 * n_blocks); memcpy(defined, back + 4 * down_words + 32 * n_blocks, n_blocks); }
-  senders_keep_head((const uint32_t *)(back + 4 * BH_WORDS));
-  const uint8_t *b = back + 8 * BH_WORDS;
-  if (txhash) memcpy(txhash, b, 32 * n);
-  memcpy(froms, b + 32 * n, 20 * n); memcpy(rec_froms, b + 52 * n, 20 * m); memset(rec_froms + 20 * m, 0, 20 * (n - m)); memcpy(rec_of, b + 72 * n, 4 * n);
-  const uint32_t *prefix = (const uint32_t *)(b + 76 * n); const uint8_t *bst = b + 76 * n + 4 * (n + 1);
-  memcpy(status, bst, n); memcpy(code, bst + 4 * okw, n); if (m) memcpy(recs, back + 4 * small_words, 4 * (size_t)REC_WORDS * m);
+  if (n_blocks) { memcpy(rq->roots, roots_back, 32 * n_blocks); memcpy(rq->defined, roots_back + 4 * (L.trie.defined - L.trie.roots), n_blocks); }
+  senders_keep_head((const uint32_t *)g.host(L.sp_head));
+  if (o.txhash) memcpy(o.txhash, g.host(L.txhash), 32 * n);
+  memcpy(o.froms, g.host(L.froms), 20 * n); memcpy(o.rec_froms, g.host(L.rec_froms), 20 * m); memset(o.rec_froms + 20 * m, 0, 20 * (n - m)); memcpy(o.rec_of, g.host(L.rec_of), 4 * n);
+  const uint32_t *prefix = (const uint32_t *)g.host(L.prefix);
+  memcpy(o.status, g.host(L.status), n); memcpy(o.code, g.host(L.code), n); if (m) memcpy(o.recs, g.host(L.recs), 4 * (size_t)REC_WORDS * m);
   if (prefix[n] != m) throw GpuError("txs: the prefix values left by the device do not end at the record count");
   for (size_t k = 0; k < n_borders; k++) rec_borders[k] = (int)prefix[borders[k]];
   if (first_bad) *first_bad = head[BH_FIRST_BAD];
@@ -750,15 +729,12 @@ void probe_keccak256(const uint8_t *msgs, const uint64_t *off, size_t n, uint8_t
   for (size_t i = 0; i < n; i++) if (off[i + 1] < off[i]) throw GpuError("probe_keccak256: offsets decrease");
   if (off[n] > off[0] && !msgs) throw GpuError("probe_keccak256: a null pointer");
   if (n > 0x3FFFFFFFu) throw GpuError("probe_keccak256: more than 2^30 - 1 strings");
-  LaneScope lane(0); hipStream_t s = gpu().stream; Txs &d = txs_state(); uint8_t *back = nullptr;
-  const size_t up = stage(d, msgs, off, n, 32 * n, &back), total8 = up - 8 * (n + 1), words = up / 4 + 8 * n + 2;
-  d.grow(words); uint32_t *p = d.io.get(); if (!p) throw GpuError("txs: no workspace");
-  SyncAtExit sync;
-  HIP_CHECK(hipMemcpyAsync(p, d.pin, up, hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(k_tx_keccak, dim3(cdiv(n, TX_THREADS)), dim3(TX_THREADS), 0, s, (const uint8_t *)p, (const uint64_t *)((const uint8_t *)p + total8), (uint32_t)n, p + up / 4);
+  LaneScope lane(0); hipStream_t s = gpu().stream; const KeccakLayout L = keccak_layout(n, (size_t)(off[n] - off[0]));
+  const Staged g(L, msgs, off, n, nullptr, s);
+  hipLaunchKernelGGL(k_tx_keccak, dim3(cdiv(n, TX_THREADS)), dim3(TX_THREADS), 0, s, g.dtx, g.doff, (uint32_t)n, g.dev(L.out));
   HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipMemcpyAsync(back, p + up / 4, 32 * n, hipMemcpyDeviceToHost, s)); HIP_CHECK(hipStreamSynchronize(s));
-  memcpy(out, back, 32 * n);
+  HIP_CHECK(hipMemcpyAsync(g.back, g.dev(L.down), 4 * (L.down_end - L.down), hipMemcpyDeviceToHost, s)); HIP_CHECK(hipStreamSynchronize(s));
+  memcpy(out, g.host(L.out), 32 * n);
 }
 
 }  // namespace zk

@@ -141,6 +141,38 @@ def test_the_calls_of_zk_txs_and_zk_bodies_give_the_same_bytes_before_and_after(
     before = snap(); rc, roots, defined = e.tx_roots(body, [0, 100, 160]); assert rc == 0 and not defined.any()
     rng = random.Random(65); device_roots(e, [[rng.randbytes(64) for _ in range(5000)]]); assert snap() == before
 
+# ---- the residues of the workspace layouts ------------------------------------------------------------------------------------------------------------------------------
+def cuts(rng, n, n_lists):
+    """n_lists lists over n values, empty ones among them: n_lists + 1 entries from 0 to n, not decreasing"""
+    return [0] + sorted(rng.randrange(n + 1) for _ in range(n_lists - 1)) + [n]
+
+def test_every_residue_of_n_and_of_the_list_count(e, pool):
+    """n = 1 .. 9 transactions in 1 .. 9 blocks: n mod 4 and mod 2, 65 n mod 4 and the block count mod 8 are where a region of the workspace or an output in the
+    download moves by a padding (csrc/txs_layout.hpp); the other tests step n by wave and workgroup borders.  Every call of zk_txs.h, zk_bodies.h and zk_tx_roots.h
+    against its model, byte for byte; verifyChainBodiesRoots on public transactions only — no record, so no proof and no key — on a fresh tree and account table: the
+    one road to the records with the roots beside them."""
+    from test_gpu_bodies import check
+    DEPTH = 5
+    z = e.Zk(); many = hasher(e); S, CID = pool.signer, pool.chain_id; rng = random.Random(67); tree = e.Tree(DEPTH); accts = e.AccountTable(); memo = {}
+    def model(f, raw):                                                                               # the model decides each distinct transaction once
+        if (f, raw) not in memo: memo[f, raw] = f(raw, S, CID)
+        return memo[f, raw]
+    for n in range(1, 10):
+        body = pool.body(("zprzpzzrp" * 2)[n:2 * n]); public = pool.body("p" * n)[n % 3:] + pool.body("p" * n)[:n % 3]
+        rc, o = e.tx_signing_inputs(body, S, CID); want = [model(t.signing_inputs, r) for r in body]; assert rc == sum(w["status"] == t.OK for w in want), n
+        for got, key in (("txhash", "txhash"), ("sighash", "sighash"), ("sigs", "sig"), ("deposit_from", "deposit_from")): assert o[got].tobytes() == b"".join(w[key] for w in want), (n, got)
+        assert list(o["code"]) == [w["code"] for w in want] and list(o["status"]) == [w["status"] for w in want], n
+        rc, o = e.tx_senders(body, S, CID); want = [model(t.sender, r) for r in body]; assert rc == sum(w[0] == t.OK for w in want), n
+        assert (list(o["status"]), list(o["code"]), o["txhash"].tobytes(), o["froms"].tobytes()) == ([w[0] for w in want], [w[1] for w in want], b"".join(w[2] for w in want), b"".join(w[3] for w in want)), n
+        check(e, body, S, CID, n)
+        recs, rec_froms, rec_of, froms, code, status, txhash = bm.records(public, S, CID); assert not recs and status == [t.OK] * n
+        for n_lists in range(1, 10):
+            first = cuts(rng, n, n_lists); assert z.TxRoots(body, first) == rm.tx_roots(body, first, keccak_many=many), (n, first)
+            roots, defined = rm.tx_roots(public, first, keccak_many=many); assert all(defined)
+            rc, o = z.VerifyChainBodiesRoots(None, public, first, roots, S, CID, accts, tree.h, None, 8, None, fill=0xA5); assert rc == n_lists, (n, first, rc, e.lib().zkgpu_last_error())
+            assert (o["roots"], o["root_ok"], o["txhash"], o["froms"], o["code"], o["status"], o["n_recs"]) == (roots, [True] * n_lists, txhash, froms, code, status, 0), (n, first)
+    assert tree.size() == 0 and accts.size() == 0; accts.close(); tree.close()
+
 # ---- child-process legs -------------------------------------------------------------------------------------------------------------------------------------------------
 def leg_poison(tmp):
     """every device allocation of this process starts full of 0xA5 bytes (ZK_DEBUG_POISON_ALLOC=1): what the kernels leave unwritten would show in the roots"""

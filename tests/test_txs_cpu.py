@@ -155,3 +155,12 @@ def test_txs_entries_without_a_device(e, tmp_path):
     script = tmp_path / "no_device.py"; script.write_text(NO_DEVICE); keys = tmp_path / "keys"; keys.mkdir()
     r = subprocess.run([sys.executable, str(script), ROOT], capture_output=True, text=True, timeout=120, env=dict(os.environ, HIP_VISIBLE_DEVICES="", ZK_PRFKEY_DIR=str(keys)))
     assert r.returncode == 0 and "NO DEVICE OK" in r.stdout, (r.returncode, r.stdout[-1500:], r.stderr[-3000:])
+
+def test_workspace_layouts_under_sanitizers(tmp_path):
+    """txs_layout.hpp (the workspace of every call of gpu_txs.hip, carved once) as a program of its own under ASan + UBSan: over n, byte totals, list counts and flags
+    the regions ascend without overlap inside the workspace, the 64-bit regions are aligned, and every size and offset is the one the host functions were written with"""
+    exe = str(tmp_path / "txs_layout_driver")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
+                           "-I", os.path.join(ROOT, "blockmaze_amd", "csrc"), os.path.join(ROOT, "tests", "txs_layout_driver.cpp"), "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "TXS LAYOUT OK" in r.stdout, (r.returncode, r.stdout[-1500:], r.stderr[-3000:])
