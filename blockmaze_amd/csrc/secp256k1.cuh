@@ -85,7 +85,8 @@ template <class P, int HW> __device__ __forceinline__ void fold(const uint32_t (
 // leaves at most 2 words (p: 1 bit, N: 4 bits); fold 3 leaves a carry of 0 or 1, and where it is 1 the low words are below 2^(bits(C) + 32), so adding C once more
 // cannot carry.  Then one conditional subtraction.
 // (That last carry cannot be 1 for p: fold 3 adds less than 2^34 to a value that, where fold 2 carried, is below 2^67.  For N it needs the low 256 bits after fold 2
-// within 2^133 of 2^256, about one product in 2^120: no test reaches it, the argument above is what stands for it.)
+// within 2^133 of 2^256, about one product in 2^120 at random; tests/test_gpu_senders.py reaches it with constructed operands, in the raw products and inside the
+// recovery: test_raw_products_on_every_path_of_the_reduction, test_crafted_signatures_take_the_reduction_carries_inside_the_recovery.)
 template <class P> __device__ __forceinline__ U256 reduce512(const uint32_t (&t)[16]) {
   constexpr int CW = P::CW, O2 = fold_over(CW + 1, CW); uint32_t lo[8], hi[8], a[8], over1[CW + 1], b[8], over2[O2], c[8], over3[1];
 #pragma unroll

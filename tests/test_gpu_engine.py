@@ -180,7 +180,7 @@ def test_domain_transforms_match_oracle(m):
     for op in ("fft", "ifft", "cosetfft", "icosetfft"):
         assert np.array_equal(e.domain_transform(m, op, a), o.domain_op(op, m, a)), (m, op)
 
-@pytest.mark.parametrize("m", [16, 64, 1024, 4096, 5120, 1 << 13])
+@pytest.mark.parametrize("m", [16, 64, 1024, 2048, 4096, 5120, 1 << 13])
 def test_domain_transforms_match_oracle_at_the_top_of_the_field(m):
     """coefficients that push the lazy butterflies of the tiles (ntt.cuh: no reduction inside a tile, "25 r after eleven stages") towards their bound, where random
     ones stay in the middle: every element r - 1, 0 and r - 1 in turn, and a single r - 1 at index 0, 1 and m - 1"""

@@ -51,6 +51,32 @@ def test_raw_field_and_scalar_operations_at_the_contract_edges(e):
     assert e.secp_ops("fq_sqrt", fq) == [pow(a, (P + 1) // 4, P) for a in fq]
     assert e.secp_ops("n_inv", fn) == [pow(a, N - 2, N) for a in fn]
 
+def test_raw_products_on_every_path_of_the_reduction(e):
+    """reduce512's carries, reached on purpose (tests/secp_model.py fold_trace and reduce_cases; tests/test_secp_reduce_cpu.py shows on the CPU that every class is
+    delivered and that a dropped carry is wrong on all of it): the fold-2 carries 0, 1, 2 and the fold-3 carry modulo N, also with a = 2^256 - 1; the fold-2 carry
+    modulo p; the final subtraction after a product with a non-zero high half, both moduli.  Every case of every class goes to both products, one call an operation;
+    the squares a^2 = C + d and a^2 = epsilon go to fq_sqr."""
+    cases = [ab for name in m.REDUCE_CLASSES for ab in m.reduce_cases(name)[0]]; assert len(cases) == 64 * len(m.REDUCE_CLASSES) == 768
+    A = [a for a, _ in cases]; B = [b for _, b in cases]
+    assert e.secp_ops("n_mul", A, B) == [a * b % N for a, b in cases]
+    assert e.secp_ops("fq_mul", A, B) == [a * b % P for a, b in cases]
+    sq = [a for name in ("p sqr (1,0)", "p sqr sub") for a, _ in m.reduce_cases(name)[0]]; assert len(sq) == 128
+    assert e.secp_ops("fq_sqr", sq) == [a * a % P for a in sq]
+
+def test_crafted_signatures_take_the_reduction_carries_inside_the_recovery(e):
+    """zkRecoverSenders on signatures whose u1 = -m / r, u2 = s / r or both take the fold-3 carry, or the final subtraction after a non-zero high half
+    (secp_model.crafted_signatures: 64 of each of five kinds).  A dropped carry changes u1 or u2 by C and gives another key.  The lines with a low s go in one call
+    with homestead on; the fold-3 carry in u2 needs s above N / 2 (test_secp_reduce_cpu.py: test_a_low_s_cannot_reach_the_fold_3_carry), so those go in one
+    call with homestead off.  Both again without pubs.  ok, keys and addresses against the model on every line."""
+    lines = m.crafted_signatures(); want = m.crafted_expected(); z = e.Zk(); assert len(lines) == 320 and 10 * sum(w[0] for w in want) >= 9 * len(want)
+    for hs in (True, False):
+        idx = [i for i, l in enumerate(lines) if l[1] == hs]; assert len(idx) >= 128
+        froms, pubs, ok = z.RecoverSenders([lines[i][2] for i in idx], [lines[i][3] for i in idx], homestead=hs)
+        assert ok == [want[i][0] for i in idx]
+        assert pubs == [want[i][1].to_bytes(32, "big") + want[i][2].to_bytes(32, "big") for i in idx] and froms == [want[i][3] for i in idx]
+        froms2, none, ok2 = z.RecoverSenders([lines[i][2] for i in idx], [lines[i][3] for i in idx], homestead=hs, want_pubs=False)
+        assert none is None and (froms2, ok2) == (froms, ok)
+
 def test_resident_table_of_g(e):
     assert e.secp_gtable() == [m.mul(k, m.G) for k in range(1, 16)]
 
