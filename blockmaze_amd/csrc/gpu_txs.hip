@@ -17,6 +17,8 @@
 //   k_trie_leaf     a lane a value: the hash of its leaf in the block's Merkle-Patricia trie (DeriveSha), at its position in the sorted order of the keys
 //   k_trie_level    once a key nibble depth, deepest first: the branch, and the extension around it, at the head of every run of keys that is one
 //   k_trie_finish   a lane a block: its root
+// and, for zkHeaders (include/zk_headers.h), on the same head reader and the same sponge over a second source type
+//   k_hdr_walk, k_hdr_hash, k_hdr_finish   (described where they stand)
 // Rules every kernel keeps: no lane waits for another lane; every loop is bounded by a constant or by the transaction's own length; every
 // offset taken from the input is checked against the end of its list — and so against the transaction's end — before the byte there is read; the Keccak state is
 // indexed by compile-time constants only; no kernel uses scratch.
@@ -208,7 +210,8 @@ __device__ __forceinline__ uint64_t bs_word(const ByteSource &m, uint64_t j, uin
   return w;
 }
 // rate 136, capacity 512, 32 bytes out: total / 136 + 1 blocks, the last one padded pad ... 0x80; out[k]: bytes 4k .. 4k+3 of the digest as they lie in memory
-__device__ __forceinline__ void sponge256(const ByteSource &m, uint32_t pad, uint32_t (&out)[8]) {
+// (Src: ByteSource, or the headers' HdrSource below, through their own bs_total and bs_word)
+template <class Src> __device__ __forceinline__ void sponge256(const Src &m, uint32_t pad, uint32_t (&out)[8]) {
   uint64_t s[25];
 #pragma unroll
   for (int k = 0; k < 25; k++) s[k] = 0;
@@ -579,6 +582,212 @@ __global__ void __launch_bounds__(TX_THREADS) k_trie_finish(uint32_t n_lists, co
   if (defined) defined[b] = good ? 1 : 0;
 }
 
+// ---- headers from their bytes (include/zk_headers.h) -----------------------------------------------------------------------------------------------
+// rlp.DecodeBytes into types.Header (core/types/block.go:72-90), Header.Hash() (:105-107), Clique's verifyHeader (consensus/clique/clique.go:269-326),
+// verifyCascadingFields (:332-350), sigHash (:147-169) and ecrecover (:172-194) for n headers, one lane a header:
+//   k_hdr_walk     the 17 headers of types.Header and every rule of the strict decoder, then verifyHeader's own rules; the status so far, the byte ranges of fields
+//                  0 .. 11 and 13 .. 14 and Extra's content into a descriptor; R || S and the recovery byte from Extra's tail into the layout the recovery reads;
+//                  the fixed-size outputs
+//   k_hdr_hash     2n jobs, lanes 0 .. n-1 the seal hash (a fresh list header, fields 0 .. 11, a fresh string header, Extra less 65 bytes, fields 13 .. 14), lanes
+//                  n .. 2n-1 the hash of the header's bytes as they stand
+//   (the recovery's six launches on the seal hashes, homestead = false)
+//   k_hdr_finish   the link and the timestamp rule against lane i - 1's hash, number and time (the caller's parent for lane 0); the recovery's verdict and the
+//                  recovery-id rule; the first header whose status is not OK
+enum { HDR_OK = 0, HDR_MALFORMED, HDR_FUTURE, HDR_CHECKPOINT_BENEFICIARY, HDR_VOTE, HDR_CHECKPOINT_VOTE, HDR_VANITY, HDR_SIGNATURE, HDR_EXTRA_SIGNERS, HDR_CHECKPOINT_SIGNERS,
+       HDR_MIX_DIGEST, HDR_UNCLE_HASH, HDR_DIFFICULTY, HDR_ANCESTOR, HDR_TIMESTAMP, HDR_SEAL, HDR_SEAL_UNDECIDED };
+static_assert(HDR_MALFORMED == ZK_HDR_MALFORMED && HDR_DIFFICULTY == ZK_HDR_DIFFICULTY && HDR_SEAL_UNDECIDED == ZK_HDR_SEAL_UNDECIDED, "zk_headers.h names these");
+// the descriptor of a lane, in words; word k of lane i lies at H[k * n + i]: the status so far | where field 0 starts | where field 11 ends (Extra's own header starts) |
+// where field 13 starts | where field 14 ends | Extra's content
+constexpr int HD_META = 0, HD_A = 1, HD_B = 2, HD_C = 3, HD_E = 4, HD_XB = 5, HD_XS = 6, HD_WORDS = 7;
+enum { HK_HASH, HK_ADDR, HK_BLOOM, HK_NONCE, HK_BIG, HK_U64, HK_BYTES, HK_HASHES };
+constexpr int HDR_FIELDS = 17, HF_UNCLE = 1, HF_COINBASE = 2, HF_TXHASH = 4, HF_DIFFICULTY = 7, HF_NUMBER = 8, HF_TIME = 11, HF_EXTRA = 12, HF_MIX = 13, HF_NONCE = 14, HF_RTCMT = 15, HF_CMT = 16;
+constexpr int HKINDS[HDR_FIELDS] = {HK_HASH, HK_HASH, HK_ADDR, HK_HASH, HK_HASH, HK_HASH, HK_BLOOM, HK_BIG, HK_BIG, HK_U64, HK_U64, HK_BIG, HK_BYTES, HK_HASH, HK_NONCE, HK_HASH, HK_HASHES};
+constexpr uint64_t HK_ALL = fk_pack(HKINDS, 0, HDR_FIELDS);                                        // block.go:72-90, three bits a field
+constexpr uint32_t HDR_VANITY_BYTES = 32, HDR_SEAL_BYTES = 65;                                     // clique.go:59-60
+constexpr uint32_t P_MINUS_N[8] = {0x2FC9BAEEu, 0x402DA172u, 0x50B75FC4u, 0x45512319u, 0x00000001u, 0, 0, 0};   // recovery/main_impl.h:105: secp256k1_ecdsa_const_p_minus_order
+// the per-header outputs of zk_headers.h on the device (HeadersLayout's download)
+struct HdrOut { uint32_t *hash, *sealhash, *signer, *coinbase, *tx_root, *rtcmt; uint64_t *number, *time; uint32_t *extra_beg, *extra_size, *cmt_beg, *cmt_count; uint8_t *difficulty, *vote, *status; };
+struct HdrParent { uint32_t have, hash[8]; uint64_t number, time; };                              // hash: bytes 4k .. 4k+3 as they lie in memory
+// the OR and the AND of count bytes at beg; count is a constant at every call
+__device__ __forceinline__ uint32_t hdr_or(const uint8_t *__restrict__ t, uint32_t beg, uint32_t count) { uint32_t v = 0;
+#pragma unroll 4
+  for (uint32_t k = 0; k < count; k++) v |= t[beg + k];
+  return v; }
+__device__ __forceinline__ uint32_t hdr_and(const uint8_t *__restrict__ t, uint32_t beg, uint32_t count) { uint32_t v = 0xFFu;
+#pragma unroll 4
+  for (uint32_t k = 0; k < count; k++) v &= t[beg + k];
+  return v; }
+// four bytes as they lie in memory; `want` false: zero, and nothing is read
+__device__ __forceinline__ uint32_t hdr_le32(const uint8_t *__restrict__ t, uint32_t beg, bool want) {
+  return want ? (uint32_t)t[beg] | ((uint32_t)t[beg + 1] << 8) | ((uint32_t)t[beg + 2] << 16) | ((uint32_t)t[beg + 3] << 24) : 0u; }
+__global__ void __launch_bounds__(TX_THREADS) k_hdr_walk(const uint8_t *__restrict__ hdrs, const uint64_t *__restrict__ off, uint32_t n, uint64_t epoch, uint64_t now, uint32_t *__restrict__ H,
+                                                          uint8_t *__restrict__ rs, uint8_t *__restrict__ vout, HdrOut o, uint32_t *__restrict__ first_bad) {
+  const uint32_t i = blockIdx.x * TX_THREADS + threadIdx.x; if (i >= n) return;
+  if (i == 0) first_bad[0] = n;                                                                    // k_hdr_finish's atomicMin starts from "none"
+  const uint64_t base = off[0], o0 = off[i] - base, len64 = off[i + 1] - off[i]; const uint8_t *t = hdrs + o0;   // (the host has checked that off does not decrease)
+  bool bad = len64 == 0 || len64 > 0xFFFFFFFFull; const uint32_t len = (uint32_t)len64;            // (this library's bound)
+  uint32_t pos = 0, lim = 0, a = 0, b = 0, c = 0, e = 0, xb = 0, xs = 0, uncle = 0, coin = 0, txr = 0, dbeg = 0, dsize = 0, nbeg = 0, nsize = 0, tbeg = 0, tsize = 0, mix = 0, nonce = 0, rt = 0,
+           cb = 0, cs = 0;
+  if (!bad) { const Head h = tx_head(t, 0, len);                                                    // the outer item: a list (decode.go:438, :762) that ends where the input ends (:142-144)
+    bad = h.bad || h.kind != K_LIST || h.beg + h.size != len; pos = h.beg; lim = len; a = pos; }
+#pragma unroll 1
+  for (int f = 0; f < HDR_FIELDS && !bad; f++) {
+    if (pos == lim) { bad = true; break; }                                                          // :443-444: too few elements
+    const Head h = tx_head(t, pos, lim); if (h.bad) { bad = true; break; }
+    const uint32_t kind = (uint32_t)((HK_ALL >> (3 * f)) & 7u); pos = h.beg + h.size;
+    switch (kind) {
+      case HK_HASH: bad = h.kind != K_STR || h.size != 32; break;                                   // decodeByteArray :395-430: a lone byte and a list are refused
+      case HK_ADDR: bad = h.kind != K_STR || h.size != 20; break;
+      case HK_BLOOM: bad = h.kind != K_STR || h.size != 256; break;
+      case HK_NONCE: bad = h.kind != K_STR || h.size != 8; break;
+      case HK_BIG: bad = h.kind == K_LIST || (h.size && t[h.beg] == 0); break;                      // :271-287
+      case HK_U64: bad = !tx_uint_ok(t, h, 8); break;                                               // :703-734
+      case HK_BYTES: bad = h.kind == K_LIST; break;                                                 // :386-393
+      default:                                                                                      // []*common.Hash: :323-336, makePtrDecoder :456-478, then :395-430
+        bad = h.kind != K_LIST;
+        if (!bad) { uint32_t p = h.beg; const uint32_t end = h.beg + h.size;
+#pragma unroll 1
+          while (p < end) { const Head u = tx_head(t, p, end); if (u.bad || u.kind != K_STR || u.size != 32) { bad = true; break; } p = u.beg + u.size; } }   // (p grows by 33 a turn)
+        break;
+    }
+    if (f == HF_UNCLE) uncle = h.beg;
+    if (f == HF_COINBASE) coin = h.beg;
+    if (f == HF_TXHASH) txr = h.beg;
+    if (f == HF_DIFFICULTY) { dbeg = h.beg; dsize = h.size; }
+    if (f == HF_NUMBER) { nbeg = h.beg; nsize = h.size; if (nsize > 8) bad = true; }                // (this library's bound: the reference reads Number.Uint64())
+    if (f == HF_TIME) { tbeg = h.beg; tsize = h.size; b = pos; }
+    if (f == HF_EXTRA) { xb = h.beg; xs = h.size; c = pos; }
+    if (f == HF_MIX) mix = h.beg;
+    if (f == HF_NONCE) { nonce = h.beg; e = pos; }
+    if (f == HF_RTCMT) rt = h.beg;
+    if (f == HF_CMT) { cb = h.beg; cs = h.size; }
+  }
+  if (!bad && pos != lim) bad = true;                                                               // :449, :778: too many elements
+  const bool good = !bad; uint64_t number = 0, time = 0; uint32_t status = HDR_MALFORMED, diff = 0, vote = 0;
+  if (good) {
+    const uint32_t tk = tsize < 8u ? tsize : 8u, tfrom = tbeg + tsize - tk;                         // Time.Uint64(): the low 64 bits
+#pragma unroll
+    for (uint32_t k = 0; k < 8; k++) { if (k < nsize) number = (number << 8) | t[nbeg + k]; if (k < tk) time = (time << 8) | t[tfrom + k]; }
+    diff = dsize == 0 ? 0u : dsize == 1 ? (uint32_t)t[dbeg] : 255u;                                 // (1 and 2 are themselves; whatever is wider is neither)
+    const bool checkpoint = number % epoch == 0;                                                    // clique.go:280
+    const uint32_t nonce_or = hdr_or(t, nonce, 8), nonce_and = hdr_and(t, nonce, 8); vote = nonce_and == 0xFFu ? 1u : 0u;
+    bool uncle_ok = true;                                                                           // :65: Keccak256(c0)
+    constexpr uint32_t UNCLE[8] = {0xe84dcc1du, 0x7a5dc7deu, 0x67b585abu, 0x1ad4ccb6u, 0x1b4512d3u, 0x13748a94u, 0xfd42a1f0u, 0x4793d440u};
+#pragma unroll
+    for (uint32_t k = 0; k < 8; k++) uncle_ok = uncle_ok && hdr_le32(t, uncle + 4 * k, true) == UNCLE[k];
+    status = (tsize > 8 || time > now) ? HDR_FUTURE                                                 // :276
+           : (checkpoint && hdr_or(t, coin, 20)) ? HDR_CHECKPOINT_BENEFICIARY                       // :281
+           : (nonce_and != 0xFFu && nonce_or != 0) ? HDR_VOTE                                       // :285
+           : (checkpoint && nonce_or != 0) ? HDR_CHECKPOINT_VOTE                                    // :288
+           : xs < HDR_VANITY_BYTES ? HDR_VANITY                                                     // :292
+           : xs < HDR_VANITY_BYTES + HDR_SEAL_BYTES ? HDR_SIGNATURE                                 // :295
+           : (!checkpoint && xs != HDR_VANITY_BYTES + HDR_SEAL_BYTES) ? HDR_EXTRA_SIGNERS           // :300
+           : (checkpoint && (xs - HDR_VANITY_BYTES - HDR_SEAL_BYTES) % 20u) ? HDR_CHECKPOINT_SIGNERS   // :303
+           : hdr_or(t, mix, 32) ? HDR_MIX_DIGEST                                                    // :307
+           : !uncle_ok ? HDR_UNCLE_HASH                                                             // :311
+           : (number > 0 && diff != 1 && diff != 2) ? HDR_DIFFICULTY : HDR_OK;                      // :315-318
+  }
+  const size_t nn = n;
+  H[HD_META * nn + i] = status; H[HD_A * nn + i] = a; H[HD_B * nn + i] = b; H[HD_C * nn + i] = c; H[HD_E * nn + i] = e; H[HD_XB * nn + i] = xb; H[HD_XS * nn + i] = xs;
+  const bool sealed = good && xs >= HDR_SEAL_BYTES; const uint32_t tail = sealed ? xb + xs - HDR_SEAL_BYTES : 0u;   // R || S || the recovery byte: Extra's last 65 (clique.go:182)
+#pragma unroll 4
+  for (uint32_t k = 0; k < 64; k++) rs[64 * (size_t)i + k] = sealed ? t[tail + k] : (uint8_t)0;
+  vout[i] = sealed ? t[tail + 64] : (uint8_t)0;
+#pragma unroll
+  for (uint32_t k = 0; k < 8; k++) { o.tx_root[8 * (size_t)i + k] = hdr_le32(t, txr + 4 * k, good); o.rtcmt[8 * (size_t)i + k] = hdr_le32(t, rt + 4 * k, good); }
+#pragma unroll
+  for (uint32_t k = 0; k < 5; k++) o.coinbase[5 * (size_t)i + k] = hdr_le32(t, coin + 4 * k, good);
+  o.number[i] = number; o.time[i] = time; o.difficulty[i] = (uint8_t)diff; o.vote[i] = (uint8_t)vote;
+  o.extra_beg[i] = good ? xb : 0u; o.extra_size[i] = good ? xs : 0u; o.cmt_beg[i] = good ? cb : 0u; o.cmt_count[i] = good ? cs / 33u : 0u;
+}
+// The seal hash's message: pre_len bytes of pre, a[0 .. a_len), mid_len bytes of mid, x[0 .. x_len), c[0 .. c_len).  Byte k of pre and mid is bits 8k .. 8k+7.  The
+// whole header's hash is the same source with a alone.  (ByteSource has one range; this one is its own type, so that the kernels on ByteSource stay what they are.)
+struct HdrSource { uint64_t pre, mid; uint32_t pre_len, mid_len; const uint8_t *a, *x, *c; uint64_t a_len, x_len, c_len; };
+__device__ __forceinline__ uint64_t bs_total(const HdrSource &m) { return (uint64_t)m.pre_len + m.a_len + m.mid_len + m.x_len + m.c_len; }
+__device__ __forceinline__ uint64_t bs_byte(const HdrSource &m, uint64_t j, uint32_t pad) {
+  if (j < m.pre_len) return (m.pre >> (8 * j)) & 0xFFull;
+  uint64_t q = j - m.pre_len;
+  if (q < m.a_len) return (uint64_t)m.a[q];
+  q -= m.a_len;
+  if (q < m.mid_len) return (m.mid >> (8 * q)) & 0xFFull;
+  q -= m.mid_len;
+  if (q < m.x_len) return (uint64_t)m.x[q];
+  q -= m.x_len;
+  if (q < m.c_len) return (uint64_t)m.c[q];
+  return q == m.c_len ? (uint64_t)pad : 0ull;
+}
+// bytes j .. j+7 as a little-endian word: one 8-byte read where all eight lie in one of the three ranges
+__device__ __forceinline__ uint64_t bs_word(const HdrSource &m, uint64_t j, uint32_t pad) {
+  if (j >= m.pre_len) {
+    const uint64_t q = j - m.pre_len, xa = m.a_len + m.mid_len, ca = xa + m.x_len; uint64_t w;
+    if (q + 8 <= m.a_len) { __builtin_memcpy(&w, m.a + q, 8); return w; }
+    if (q >= xa && q + 8 <= ca) { __builtin_memcpy(&w, m.x + (q - xa), 8); return w; }
+    if (q >= ca && q + 8 <= ca + m.c_len) { __builtin_memcpy(&w, m.c + (q - ca), 8); return w; }
+  }
+  uint64_t w = 0;
+#pragma unroll 1
+  for (uint32_t k = 0; k < 8; k++) w |= bs_byte(m, j + k, pad) << (8 * k);
+  return w;
+}
+__global__ void __launch_bounds__(TX_THREADS) k_hdr_hash(const uint8_t *__restrict__ hdrs, const uint64_t *__restrict__ off, uint32_t n, const uint32_t *__restrict__ H, uint32_t *__restrict__ sealhash,
+                                                          uint32_t *__restrict__ hash) {
+  const uint32_t j = blockIdx.x * TX_THREADS + threadIdx.x; if (j >= 2 * n) return;
+  const bool whole = j >= n; const uint32_t i = whole ? j - n : j; const size_t nn = n; uint32_t *out = (whole ? hash : sealhash) + 8 * (size_t)i;
+  const uint32_t status = H[HD_META * nn + i], xs = H[HD_XS * nn + i];
+  if (status == HDR_MALFORMED || (!whole && xs < HDR_SEAL_BYTES)) {                                 // sigHash panics below 65 bytes (clique.go:163); ecrecover asks first (:179)
+#pragma unroll
+    for (int k = 0; k < 8; k++) out[k] = 0u;
+    return; }
+  const uint64_t o0 = off[i] - off[0]; const uint8_t *t = hdrs + o0;
+  HdrSource m; m.pre = m.mid = 0; m.pre_len = m.mid_len = 0; m.a = m.x = m.c = t; m.a_len = m.x_len = m.c_len = 0;
+  if (whole) m.a_len = off[i + 1] - off[i];                                                         // Header.Hash(): the strict decoder makes the re-encoding the input
+  else {                                                                                           // sigHash (clique.go:150-166): the upstream 15 fields, Extra less its last 65 bytes
+    const uint32_t a = H[HD_A * nn + i], b = H[HD_B * nn + i], c = H[HD_C * nn + i], e = H[HD_E * nn + i], xb = H[HD_XB * nn + i], rest = xs - HDR_SEAL_BYTES; uint32_t cnt;
+    m.a = t + a; m.a_len = b - a; m.x = t + xb; m.x_len = rest; m.c = t + c; m.c_len = e - c;
+    if (rest == 0) { m.mid = 0x80ull; m.mid_len = 1; }
+    else if (rest == 1 && t[xb] < 0x80u) { }                                                        // the byte is its own encoding
+    else if (rest < 56) { m.mid = 0x80ull + rest; m.mid_len = 1; }
+    else { const uint64_t l = be_bytes(rest, &cnt); m.mid = (0xB7ull + cnt) | (l << 8); m.mid_len = 1 + cnt; }   // cnt <= 4
+    const uint64_t payload = m.a_len + m.mid_len + m.x_len + m.c_len;                               // above 55 (the bloom alone), below the header's length
+    const uint64_t l = be_bytes(payload, &cnt); m.pre = (0xF7ull + cnt) | (l << 8); m.pre_len = 1 + cnt;   // cnt <= 4
+  }
+  uint32_t h[8]; sponge256(m, 0x01u, h);
+#pragma unroll
+  for (int k = 0; k < 8; k++) out[k] = h[k];
+}
+__global__ void __launch_bounds__(TX_THREADS) k_hdr_finish(const uint8_t *__restrict__ hdrs, const uint64_t *__restrict__ off, uint32_t n, uint64_t period, HdrParent parent, const uint32_t *__restrict__ H,
+                                                            const uint32_t *__restrict__ rs, const uint8_t *__restrict__ v, const uint8_t *__restrict__ ok, const uint32_t *__restrict__ recovered,
+                                                            HdrOut o, const uint32_t *__restrict__ sp_head, uint32_t *__restrict__ head) {
+  const uint32_t i = blockIdx.x * TX_THREADS + threadIdx.x; if (i >= n) return;
+  if (i == 0) {                                                                                     // the recovery's four counters ride in the one download
+#pragma unroll
+    for (int k = 0; k < 4; k++) head[BH_WORDS + k] = sp_head[k]; }
+  const size_t nn = n; uint32_t status = H[HD_META * nn + i], f[5] = {0, 0, 0, 0, 0}; const uint64_t number = o.number[i];
+  if (status == HDR_OK && number > 0) {                                                             // clique.go:334-336: the genesis is the always valid dead end
+    const uint8_t *t = hdrs + (off[i] - off[0]); const uint32_t ph = H[HD_A * nn + i] + 1;          // ParentHash's 32 bytes: field 0, behind its one header byte
+    bool have = i ? H[HD_META * nn + (i - 1)] != HDR_MALFORMED : parent.have != 0;                  // :340-343: headers[:i]'s last, or what the caller found; a malformed one is no header
+    const uint64_t pnumber = i ? o.number[i - 1] : parent.number, ptime = i ? o.time[i - 1] : parent.time;
+    bool link = have && pnumber == number - 1;                                                      // :345
+#pragma unroll
+    for (uint32_t k = 0; k < 8; k++) link = link && hdr_le32(t, ph + 4 * k, true) == (i ? o.hash[8 * (size_t)(i - 1) + k] : parent.hash[k]);
+    if (!link) status = HDR_ANCESTOR;
+    else if (ptime + period > o.time[i]) status = HDR_TIMESTAMP;                                    // :348: uint64, the wrap included (FUTURE has refused a wider Time)
+    else {                                                                                          // crypto.Ecrecover(sigHash, Extra[len - 65:]) (:185)
+      const secp::U256 r = secp::load_be(rs + 16 * (size_t)i), s = secp::load_be(rs + 16 * (size_t)i + 8); const uint32_t vb = v[i];
+      if (vb >= 4 || secp::u256_is_zero(r) || secp::u256_is_zero(s) || secp::u256_geq(r, secp::FnP::MOD) || secp::u256_geq(s, secp::FnP::MOD)) status = HDR_SEAL;   // secp256.go:175; main_impl.h:48-51, :96-98
+      else if (vb & 2u) status = secp::u256_geq(r, P_MINUS_N) ? HDR_SEAL : HDR_SEAL_UNDECIDED;      // main_impl.h:104-107; x = r + N is not taken here: the caller decides
+      else if (ok[i]) {
+#pragma unroll
+        for (int k = 0; k < 5; k++) f[k] = recovered[5 * (size_t)i + k]; }
+      else status = HDR_SEAL;                                                                       // main_impl.h:110, :120
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 5; k++) o.signer[5 * (size_t)i + k] = f[k];
+  o.status[i] = (uint8_t)status;
+  if (status != HDR_OK) atomicMin(head + BH_FIRST_BAD, i);
+}
+
 // ---- the host side ------------------------------------------------------------------------------------------------------------------------------------------------
 namespace {
 struct Txs : PinnedStage {                           // one a process, every member under the device mutex
@@ -587,6 +796,7 @@ struct Txs : PinnedStage {                           // one a process, every mem
 };
 Txs &txs_state() { static Txs *t = new Txs; return *t; }   // (never destroyed: the runtime may be gone when statics are)
 static_assert(TXL_D_WORDS == TD_WORDS && TXL_E_WORDS == TE_WORDS && TXL_HEAD_WORDS == BH_WORDS && TXL_REC_WORDS == REC_WORDS && TXL_THREADS == TX_THREADS, "txs_layout.hpp carves for these kernels");
+static_assert(TXL_H_WORDS == HD_WORDS, "txs_layout.hpp carves for k_hdr_walk");
 // pinned, on a layout of txs_layout.hpp: the upload's three pieces — the bytes off[0] .. off[n) of the caller's buffer, padded to 8, off itself, the n_first entries of
 // first (checked by the caller: 0 .. n, so int and uint32_t agree), padded to 8; returns where the download will land
 uint8_t *stage(Txs &d, const TxsUpload &L, const uint8_t *bytes, const uint64_t *off, size_t n, const int *first) {
@@ -671,6 +881,36 @@ size_t tx_sender_inputs(const TxsIn &in, bool want_senders, const SenderInputsOu
   memcpy(o.status, g.host(L.status), n); memcpy(o.code, g.host(L.code), n);
   size_t good = 0; for (size_t i = 0; i < n; i++) good += o.status[i] == TX_OK;
   return good;
+}
+// zkHeaders (include/zk_headers.h).  The caller has checked the arguments and holds the device mutex; n > 0.  One upload (the headers, then off), three launches around
+// the recovery's six, one download.  Returns the number of leading headers with status OK.
+size_t headers_decide(const HeadersIn &in, const HeadersOut &o) {
+  const size_t n = in.n;
+  if (n > 0x3FFFFFFFu) throw GpuError("headers: more than 2^30 - 1 headers");
+  LaneScope lane(0); hipStream_t s = gpu().stream; const HeadersLayout L = headers_layout(n, (size_t)(in.off[n] - in.off[0]));
+  const Staged g(L, in.hdrs, in.off, n, nullptr, s);
+  uint32_t *H = g.dev(L.H), *rs = g.dev(L.rs), *v = g.dev(L.v), *rec = g.dev(L.rec), *d_head = g.dev(L.head);
+  const HdrOut d{g.dev(L.hash), g.dev(L.sealhash), g.dev(L.signer), g.dev(L.coinbase), g.dev(L.tx_root), g.dev(L.rtcmt), (uint64_t *)g.dev(L.number), (uint64_t *)g.dev(L.time), g.dev(L.extra_beg),
+                 g.dev(L.extra_size), g.dev(L.cmt_beg), g.dev(L.cmt_count), (uint8_t *)g.dev(L.difficulty), (uint8_t *)g.dev(L.vote), (uint8_t *)g.dev(L.status)};
+  HdrParent parent; parent.have = in.have_parent ? 1u : 0u; parent.number = in.parent_number; parent.time = in.parent_time; memset(parent.hash, 0, sizeof parent.hash);
+  if (in.have_parent) memcpy(parent.hash, in.parent_hash, 32);
+  const dim3 block(TX_THREADS), grid(cdiv(n, TX_THREADS)), grid2(cdiv(2 * n, TX_THREADS));
+  hipLaunchKernelGGL(k_hdr_walk, grid, block, 0, s, g.dtx, g.doff, (uint32_t)n, in.epoch ? in.epoch : (uint64_t)30000, in.now, H, (uint8_t *)rs, (uint8_t *)v, d, d_head + BH_FIRST_BAD);   // clique.go:56, :217-219
+  hipLaunchKernelGGL(k_hdr_hash, grid2, block, 0, s, g.dtx, g.doff, (uint32_t)n, (const uint32_t *)H, d.sealhash, d.hash);
+  HIP_CHECK(hipGetLastError());
+  recover_senders_queue(d.sealhash, rs, (const uint8_t *)v, n, false, rec, s);                      // crypto.Ecrecover: no low-s rule
+  hipLaunchKernelGGL(k_hdr_finish, grid, block, 0, s, g.dtx, g.doff, (uint32_t)n, in.period, parent, (const uint32_t *)H, (const uint32_t *)rs, (const uint8_t *)v, (const uint8_t *)g.dev(L.ok),
+                     (const uint32_t *)g.dev(L.recovered), d, (const uint32_t *)rec, d_head);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipMemcpyAsync(g.back, g.dev(L.down), 4 * (L.down_end - L.down), hipMemcpyDeviceToHost, s)); HIP_CHECK(hipStreamSynchronize(s));
+  uint32_t head[BH_WORDS]; memcpy(head, g.host(L.head), sizeof head); const size_t k = head[BH_FIRST_BAD];
+  if (k > n) throw GpuError("headers: the count left by the device is out of range");
+  senders_keep_head((const uint32_t *)g.host(L.sp_head));
+  memcpy(o.hash, g.host(L.hash), 32 * n); memcpy(o.sealhash, g.host(L.sealhash), 32 * n); memcpy(o.signer, g.host(L.signer), 20 * n); memcpy(o.coinbase, g.host(L.coinbase), 20 * n);
+  memcpy(o.tx_root, g.host(L.tx_root), 32 * n); memcpy(o.rtcmt, g.host(L.rtcmt), 32 * n); memcpy(o.number, g.host(L.number), 8 * n); memcpy(o.time, g.host(L.time), 8 * n);
+  memcpy(o.difficulty, g.host(L.difficulty), n); memcpy(o.vote, g.host(L.vote), n); memcpy(o.extra_beg, g.host(L.extra_beg), 4 * n); memcpy(o.extra_size, g.host(L.extra_size), 4 * n);
+  memcpy(o.cmt_beg, g.host(L.cmt_beg), 4 * n); memcpy(o.cmt_count, g.host(L.cmt_count), 4 * n); memcpy(o.status, g.host(L.status), n);
+  return k;
 }
 // zkTxRecords (include/zk_bodies.h).  The caller has checked the arguments and holds the device mutex.  One upload (txs, then off); the walk with both descriptors, the
 // hashes, the recovery's six launches once for all lanes, k_body_finish, k_body_scan, k_body_scatter, k_body_gather; four words that say m; one download: the small

@@ -1,4 +1,4 @@
-// What the units of the transaction calls share (gpu_txs.hip, gpu_senders.hip, capi_txs.cpp, capi_bodies.cpp, capi_tx_roots.cpp): the argument structs and the
+// What the units of the transaction calls share (gpu_txs.hip, gpu_senders.hip, capi_txs.cpp, capi_bodies.cpp, capi_tx_roots.cpp, capi_headers.cpp): the argument structs and the
 // prototypes of the functions they export to each other, and the two pieces every C entry of them starts with.  The workspace layouts: txs_layout.hpp.
 #pragma once
 #include <cstdint>
@@ -7,6 +7,7 @@
 #include "../../include/zkgpu.h"
 #include "../../include/zk_records.h"
 #include "../../include/zk_txs.h"
+#include "../../include/zk_headers.h"
 #include "gpu.hpp"
 #include "txs_layout.hpp"
 
@@ -23,9 +24,14 @@ struct BodyOut { zk_block_record *recs; uint8_t *rec_froms; int32_t *rec_of; uin
 // the trie roots of n_lists lists: first, n_lists + 1 entries from 0 to n; roots 32 bytes a list; defined a byte a list (null for zkgpu_list_trie_roots)
 struct RootsRequest { const int *first; size_t n_lists; uint8_t *roots, *defined; };
 
+// zkHeaders (include/zk_headers.h): n headers, hdrs[off[i] .. off[i+1]), the engine's two numbers, the clock, the parent of header 0; the outputs, room for n each
+struct HeadersIn { const uint8_t *hdrs; const uint64_t *off; size_t n; uint64_t period, epoch, now; int have_parent; const uint8_t *parent_hash; uint64_t parent_number, parent_time; };
+struct HeadersOut { uint8_t *hash, *sealhash, *signer, *coinbase, *tx_root, *rtcmt; uint64_t *number, *time; uint8_t *difficulty, *vote; uint32_t *extra_beg, *extra_size, *cmt_beg, *cmt_count; uint8_t *status; };
+
 // gpu_txs.hip.  The caller has checked the arguments and holds the device mutex.
 size_t tx_sender_inputs(const TxsIn &in, bool want_senders, const SenderInputsOut &o);
 size_t tx_records(const TxsIn &in, const BodyOut &o, size_t *first_bad, const int *borders, size_t n_borders, int *rec_borders, const RootsRequest *roots);
+size_t headers_decide(const HeadersIn &in, const HeadersOut &o);
 size_t trie_roots(const uint8_t *vals, const uint64_t *off, size_t n, const RootsRequest &rq, bool want_tx);
 void probe_keccak256(const uint8_t *msgs, const uint64_t *off, size_t n, uint8_t *out);
 void tx_records_gather_bytewise(bool on);

@@ -96,6 +96,26 @@ inline TrieRootsLayout trie_roots_layout(size_t n, size_t total_bytes, size_t n_
   return L;
 }
 
+// zkHeaders (include/zk_headers.h).  Device, in words: up | H, the walk's descriptor | rs 16n | v | the recovery's out | down.
+// Down, in words: head 4 (first_bad, -, -, -) | sp_head, the recovery's four | number 2n | time 2n | hash 8n | sealhash 8n (the recovery reads it where it lies) |
+// signer 5n | coinbase 5n | tx_root 8n | rtcmt 8n | extra_beg n | extra_size n | cmt_beg n | cmt_count n | then bytes: difficulty n | vote n | status n.
+constexpr size_t TXL_H_WORDS = 7;
+struct HeadersLayout : TxsUpload {
+  size_t H, rs, v, rec, ok, recovered, head, sp_head, number, time, hash, sealhash, signer, coinbase, tx_root, rtcmt, extra_beg, extra_size, cmt_beg, cmt_count, difficulty, vote, status;
+};
+inline HeadersLayout headers_layout(size_t n, size_t total_bytes) {
+  HeadersLayout L; Carve c = carve_upload(L, n, total_bytes, 0);
+  L.H = c.take(TXL_H_WORDS * n); L.rs = c.take(16 * n); L.v = c.take(Carve::bytes(n));
+  const SendersOut so = senders_out(c, n, false); L.rec = so.head; L.ok = so.ok; L.recovered = so.froms;
+  L.down = L.head = c.take(TXL_HEAD_WORDS, 2);           // (number and time are placed from here: 64-bit values on both sides of the bus)
+  L.sp_head = c.take(TXL_SP_HEAD);                       // k_hdr_finish: head[4 .. 8)
+  L.number = c.take(2 * n, 2); L.time = c.take(2 * n, 2); L.hash = c.take(8 * n); L.sealhash = c.take(8 * n); L.signer = c.take(5 * n); L.coinbase = c.take(5 * n); L.tx_root = c.take(8 * n);
+  L.rtcmt = c.take(8 * n); L.extra_beg = c.take(n); L.extra_size = c.take(n); L.cmt_beg = c.take(n); L.cmt_count = c.take(n);
+  L.difficulty = c.take(Carve::bytes(n)); L.vote = c.take(Carve::bytes(n)); L.status = c.take(Carve::bytes(n));
+  L.down_end = L.end = c.at; L.pin_bytes = L.up + 4 * (L.down_end - L.down);
+  return L;
+}
+
 // zkgpu_test_keccak256.  Device, in words: up | out 8n, which comes down.
 struct KeccakLayout : TxsUpload { size_t out; };
 inline KeccakLayout keccak_layout(size_t n, size_t total_bytes) {

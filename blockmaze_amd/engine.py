@@ -161,6 +161,26 @@ def tx_roots(txs, block_first):
     rc = int(lib().zkgpu_tx_roots(_bytes(blob), _u64p(off), n, _i32p(f), nb, _bytes(roots) if nb > 0 else None, _bytes(defined) if nb > 0 else None))
     return rc, roots, defined
 
+# headers from their bytes (csrc/gpu_txs.hip, csrc/capi_headers.cpp; include/zk_headers.h)
+(HDR_OK, HDR_MALFORMED, HDR_FUTURE, HDR_CHECKPOINT_BENEFICIARY, HDR_VOTE, HDR_CHECKPOINT_VOTE, HDR_VANITY, HDR_SIGNATURE, HDR_EXTRA_SIGNERS, HDR_CHECKPOINT_SIGNERS, HDR_MIX_DIGEST,
+ HDR_UNCLE_HASH, HDR_DIFFICULTY, HDR_ANCESTOR, HDR_TIMESTAMP, HDR_SEAL, HDR_SEAL_UNDECIDED) = range(17)
+HEADER_OUTPUTS = (("hash", 32, np.uint8), ("sealhash", 32, np.uint8), ("signer", 20, np.uint8), ("coinbase", 20, np.uint8), ("tx_root", 32, np.uint8), ("rtcmt", 32, np.uint8),
+                  ("number", 0, np.uint64), ("time", 0, np.uint64), ("difficulty", 0, np.uint8), ("vote", 0, np.uint8), ("extra_beg", 0, np.uint32), ("extra_size", 0, np.uint32),
+                  ("cmt_beg", 0, np.uint32), ("cmt_count", 0, np.uint32), ("status", 0, np.uint8))                  # in the order of zkHeaders' arguments
+def _headers_call(fn, hdrs, period, epoch, now, parent, fill, start=0):
+    """parent: None or (hash: 32 bytes, number, time).  -> (the call's return value, dict of HEADER_OUTPUTS' arrays, each handed in full of `fill` bytes)"""
+    n = len(hdrs); blob, off = _tx_blob(hdrs)
+    if start: blob = np.concatenate([np.zeros(start, dtype=np.uint8), blob]); off = off + np.uint64(start)
+    o = {k: np.frombuffer(bytes([fill]) * (np.dtype(dt).itemsize * max(1, n) * (w or 1)), dtype=dt).copy().reshape((max(1, n), w) if w else max(1, n)) for k, w, dt in HEADER_OUTPUTS}
+    ph = np.frombuffer(bytes(parent[0]), dtype=np.uint8).copy() if parent is not None else None; u64 = ctypes.c_uint64
+    rc = int(fn(_bytes(blob), _u64p(off), n, u64(period), u64(epoch), u64(now), 1 if parent is not None else 0, _bytes(ph) if ph is not None else None, u64(parent[1] if parent is not None else 0),
+                u64(parent[2] if parent is not None else 0), *[o[k].ctypes.data_as(ctypes.c_void_p) for k, _, _ in HEADER_OUTPUTS]))
+    return rc, {k: v[:n] for k, v in o.items()}
+def headers(hdrs, period, epoch, now, parent, fill=0xA5, start=0):
+    """zkgpu_headers -> (the number of leading headers with status HDR_OK or a ZKGPU_ERR_* code, dict of HEADER_OUTPUTS' arrays); start: the blob begins at this byte of its
+    buffer (off[0] = start)"""
+    f = lib().zkgpu_headers; f.restype = ctypes.c_int; return _headers_call(f, hdrs, period, epoch, now, parent, fill, start)
+
 def msm(group, points, scalars, window_bits=0, filter_ones=False):
     points = np.ascontiguousarray(points, dtype=np.uint64); scalars = np.ascontiguousarray(scalars, dtype=np.uint64); n = scalars.size // 4
     out = np.zeros(8 if group == 1 else 16, dtype=np.uint64)
@@ -985,5 +1005,13 @@ class Zk:
                         anchor_of=[int(an[j]) for j in range(k)], accts_sizes=out[0], set_sizes=(out[1] if s else None), tree_sizes=out[2],
                         roots=[bytes(roots[b]) for b in range(max(0, nb))], root_ok=[bool(rok[b]) for b in range(max(0, nb))],
                         raw=dict(recs=recs, rec_froms=rf, rec_of=of, txhash=th, froms=fr, code=code, status=st, ok=ok, anchor_of=an, roots=roots, root_ok=rok))
+    # include/zk_headers.h: a batch of headers decided from their bytes; tx_root goes into VerifyChainBodiesRoots as want_roots
+    def Headers(self, hdrs, period, epoch, now, parent):
+        """hdrs: n byte strings, one RLP header each; parent: None or (hash, number, time) of the parent of header 0.  -> (k, the leading headers with status HDR_OK, and a
+        dict: hash, sealhash, signer, coinbase, tx_root, rtcmt: [bytes]; number, time, difficulty, vote, extra_beg, extra_size, cmt_beg, cmt_count, status: [int]); raises
+        ZkGpuError where the call returns -1"""
+        self.L.zkHeaders.restype = ctypes.c_int; k, o = _headers_call(self.L.zkHeaders, hdrs, period, epoch, now, parent, 0)
+        if k < 0: raise ZkGpuError("zkHeaders: %s" % self.L.zkgpu_last_error().decode())
+        return k, {name: ([bytes(r) for r in o[name]] if w else [int(x) for x in o[name]]) for name, w, _ in HEADER_OUTPUTS}
     def VerifyDepositProofDepth(self, depth, proof, RT, pk, cmtb_old, sn_old, cmtb, sns):
         return bool(self.L.verifyDepositproofDepth(int(depth), proof.encode(), self.hx(RT), self.hx(pk), self.hx(cmtb_old), self.hx(sn_old), self.hx(cmtb), self.hx(sns)))

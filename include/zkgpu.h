@@ -456,6 +456,20 @@ int zkgpu_list_trie_roots(const uint8_t *vals, const uint64_t *off /* n + 1 */, 
 int zkgpu_tx_roots(const uint8_t *txs, const uint64_t *off /* n + 1 */, int n, const int *block_first /* n_blocks + 1 */, int n_blocks, uint8_t *roots /* n_blocks x 32 */,
                    uint8_t *defined /* n_blocks */);
 
+/* ---- headers from their bytes (the drop-in level is zk_headers.h) ------------------------------------------------------------------------------
+ * One lane a header: k_hdr_walk applies the strict RLP decoder's rules to the 17 fields of types.Header and Clique's standalone rules, and leaves a descriptor, R || S
+ * and the recovery byte from Extra's tail, and the fixed-size outputs; k_hdr_hash computes the seal hash (the upstream 15 fields, Extra less its last 65 bytes) and the
+ * header's hash through the sponge over a source of three input ranges; the recovery's six launches run on the seal hashes with homestead = 0; k_hdr_finish decides the
+ * link and the timestamp against lane i - 1 and merges the verdicts.  One upload (hdrs, then off) and one download, through pinned staging; the workspace is the one the
+ * transaction calls keep.
+ * Takes the arguments of zkHeaders (as flat arrays) and returns the number of leading headers with status ZK_HDR_OK, or ZKGPU_ERR_ARG (n < 0, a null pointer with
+ * n > 0 — parent_hash only where have_parent != 0 —, a decreasing off; decided first, before the device is asked for), ZKGPU_ERR_NO_DEVICE, ZKGPU_ERR_RUNTIME; every
+ * output is zeroed on each of them. */
+int zkgpu_headers(const uint8_t *hdrs, const uint64_t *off /* n + 1 */, int n, uint64_t period, uint64_t epoch, uint64_t now, int have_parent, const uint8_t *parent_hash /* 32 */,
+                  uint64_t parent_number, uint64_t parent_time, uint8_t *hash /* n x 32 */, uint8_t *sealhash /* n x 32 */, uint8_t *signer /* n x 20 */, uint8_t *coinbase /* n x 20 */,
+                  uint8_t *tx_root /* n x 32 */, uint8_t *rtcmt /* n x 32 */, uint64_t *number, uint64_t *time, uint8_t *difficulty, uint8_t *vote, uint32_t *extra_beg,
+                  uint32_t *extra_size, uint32_t *cmt_beg, uint32_t *cmt_count, uint8_t *status);
+
 #ifdef __cplusplus
 }
 #endif
