@@ -347,11 +347,11 @@ __global__ void __launch_bounds__(TX_THREADS) k_body_finish(uint32_t n, int home
   const int count = __syncthreads_count(has);
   if (threadIdx.x == 0) counts[blockIdx.x] = (uint32_t)count;
 }
-// an inclusive scan of one value a lane over a workgroup of T lanes through sh (T words); every lane calls it
-template <int T> __device__ __forceinline__ uint32_t block_scan_inclusive(uint32_t v, uint32_t *sh) {
+// an inclusive scan of one value a lane over a workgroup of T lanes through sh (T values); every lane calls it.  V: uint32_t, or uint64_t for the split's scans
+template <int T, class V> __device__ __forceinline__ V block_scan_inclusive(V v, V *sh) {
   sh[threadIdx.x] = v; __syncthreads();
 #pragma unroll
-  for (int d = 1; d < T; d <<= 1) { const uint32_t add = threadIdx.x >= (uint32_t)d ? sh[threadIdx.x - d] : 0u; __syncthreads(); v += add; sh[threadIdx.x] = v; __syncthreads(); }
+  for (int d = 1; d < T; d <<= 1) { const V add = threadIdx.x >= (uint32_t)d ? sh[threadIdx.x - d] : (V)0; __syncthreads(); v += add; sh[threadIdx.x] = v; __syncthreads(); }
   return v;
 }
 // bases[b] = the records before workgroup b; head[BH_M] = m.  One workgroup; cdiv(nb, 256) tiles, a carry between them; the loop's bound is the same for every lane.
@@ -788,11 +788,106 @@ __global__ void __launch_bounds__(TX_THREADS) k_hdr_finish(const uint8_t *__rest
   if (status != HDR_OK) atomicMin(head + BH_FIRST_BAD, i);
 }
 
+// ---- block bodies from their bytes (include/zk_raw_bodies.h) ---------------------------------------------------------------------------------------
+// rlp.DecodeBytes(body, &types.Body{}) (core/types/block.go:143-146: Transactions, Uncles) as far as the body's structure goes, for n_blocks bodies, and their
+// transactions packed end to end where every kernel above expects them:
+//   k_split_count    a lane a body: the outer list, the two lists in it, every element head of the first; the status, the element count, where item 0's payload lies
+//   k_split_scan     one workgroup: the exclusive scans of the counts and of the payload sizes over the blocks; n, the packed total, the largest block, the first
+//                    body that is not OK
+//   k_split_offsets  a lane a body: the walk again; off in packed coordinates, tx_beg and tx_size in the caller's, first
+//   k_split_pack     a lane an aligned 8-byte word of the packed bytes: the payloads of the OK bodies end to end
+enum { BODY_OK = 0, BODY_MALFORMED = 1, BODY_UNCLES = 2 };
+static_assert(BODY_OK == ZK_BODY_OK && BODY_MALFORMED == ZK_BODY_MALFORMED && BODY_UNCLES == ZK_BODY_UNCLES, "zk_raw_bodies.h names these");
+enum { SH_N = 0, SH_TOTAL = 2, SH_LARGEST = 4, SH_K = 5, SH_WORDS = 8 };                           // the split's head; n and the total are 64-bit values
+constexpr int SPLIT_SCAN_THREADS = 256;
+// The struct decoder (decode.go:432-454) on types.Body: the outer item a list (:438, :762) that ends where the input ends (:142-144); "too few elements" (:443-444)
+// where a field finds the list at its end, "input list has too many elements" (:449, :778) where the list goes on behind the last; both fields are slices, which want
+// a list (decodeListSlice :323-326).  Every element head of item 0 is read by Stream.Kind (:902-960) before anything of the element is decoded, so a head that is not
+// canonical or overruns the list refuses the body whatever the element is.  pay_beg, pay_size: item 0's payload, relative to the body's first byte; count: its elements.
+// All three are zero unless the status is OK.  Every turn of the walk moves p on by at least one byte.
+__global__ void __launch_bounds__(TX_THREADS) k_split_count(const uint8_t *__restrict__ raw, const uint64_t *__restrict__ body_off, uint32_t nb, uint8_t *__restrict__ status,
+                                                             uint32_t *__restrict__ count, uint32_t *__restrict__ pay_beg, uint32_t *__restrict__ pay_size) {
+  const uint32_t b = blockIdx.x * TX_THREADS + threadIdx.x; if (b >= nb) return;
+  const uint64_t o0 = body_off[b] - body_off[0], len64 = body_off[b + 1] - body_off[b]; const uint8_t *t = raw + o0;   // (the host has checked that body_off does not decrease)
+  bool bad = len64 == 0 || len64 > 0xFFFFFFFFull; const uint32_t len = (uint32_t)len64;            // an empty input: io.ErrUnexpectedEOF (:142, :910); the length: this library's bound
+  uint32_t beg = 0, size = 0, usize = 0, cnt = 0, pos = 0;
+  if (!bad) { const Head o = tx_head(t, 0, len); bad = o.bad || o.kind != K_LIST || o.beg + o.size != len; pos = o.beg; }
+  if (!bad) { const Head a = tx_head(t, pos, len);                                                  // (pos == len: tx_head refuses, "too few elements")
+    bad = a.bad || a.kind != K_LIST; beg = a.beg; size = a.size; pos = a.beg + a.size; }
+  if (!bad) { const Head u = tx_head(t, pos, len); bad = u.bad || u.kind != K_LIST || u.beg + u.size != len; usize = u.size; }   // too few; not a list; too many
+  uint32_t p = beg; const uint32_t e = beg + size;
+#pragma unroll 1
+  while (!bad && p < e) { const Head h = tx_head(t, p, e); if (h.bad) bad = true; else { p = h.beg + h.size; cnt++; } }
+  const uint32_t st = bad ? BODY_MALFORMED : usize ? BODY_UNCLES : BODY_OK; const bool ok = st == BODY_OK;   // clique.go:450-455 with block_validator.go:67: no uncle
+  status[b] = (uint8_t)st; count[b] = ok ? cnt : 0u; pay_beg[b] = ok ? beg : 0u; pay_size[b] = ok ? size : 0u;
+}
+// first[b] = the transactions before body b, base[b] = the packed bytes before it, both with an entry at nb; the head.  One workgroup; cdiv(nb, 256) tiles, a carry
+// between them; the loop's bound is the same for every lane, and every lane reaches every barrier.  nb > 0.
+__global__ void __launch_bounds__(SPLIT_SCAN_THREADS) k_split_scan(const uint8_t *__restrict__ status, const uint32_t *__restrict__ count, const uint32_t *__restrict__ pay_size, uint32_t nb,
+                                                                    uint32_t *__restrict__ first, uint64_t *__restrict__ base, uint32_t *__restrict__ head) {
+  __shared__ uint64_t sh[SPLIT_SCAN_THREADS]; __shared__ uint32_t sh_max, sh_k;
+  if (threadIdx.x == 0) { sh_max = 0; sh_k = nb; }                                                  // (seen by all behind the first scan's barriers)
+  uint64_t carry_n = 0, carry_z = 0; uint32_t largest = 0, k = nb;
+#pragma unroll 1
+  for (uint32_t tile = 0; tile < nb; tile += SPLIT_SCAN_THREADS) {
+    const uint32_t b = tile + threadIdx.x; const bool in = b < nb; const uint64_t v = in ? count[b] : 0u, z = in ? pay_size[b] : 0u;
+    const uint64_t incl_n = block_scan_inclusive<SPLIT_SCAN_THREADS>(v, sh), tile_n = sh[SPLIT_SCAN_THREADS - 1]; __syncthreads();   // (sh is written again)
+    const uint64_t incl_z = block_scan_inclusive<SPLIT_SCAN_THREADS>(z, sh), tile_z = sh[SPLIT_SCAN_THREADS - 1]; __syncthreads();
+    if (in) { const uint64_t f = carry_n + incl_n - v; first[b] = f > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)f; base[b] = carry_z + incl_z - z;   // (beyond 2^30 - 1 the host stops)
+      if ((uint32_t)v > largest) largest = (uint32_t)v;
+      if (status[b] != BODY_OK && b < k) k = b; }
+    carry_n += tile_n; carry_z += tile_z;
+  }
+  atomicMax(&sh_max, largest); atomicMin(&sh_k, k); __syncthreads();
+  if (threadIdx.x == 0) { first[nb] = carry_n > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)carry_n; base[nb] = carry_z;
+    head[SH_N] = (uint32_t)carry_n; head[SH_N + 1] = (uint32_t)(carry_n >> 32); head[SH_TOTAL] = (uint32_t)carry_z; head[SH_TOTAL + 1] = (uint32_t)(carry_z >> 32);
+    head[SH_LARGEST] = sh_max; head[SH_K] = sh_k; head[6] = 0; head[7] = 0; }
+}
+// The walk of k_split_count again over an OK body (its heads have all been accepted): element j of body b is transaction i = first[b] + j; off[i]: where it starts in
+// the packed bytes; tx_beg[i], tx_size[i]: where it lies in the caller's buffer.  off[n] and dfirst[nb] are lane 0's, whatever body 0 is; dfirst may be null.
+// i < n is compared before anything is written: n is what the host read from the scan's head.
+__global__ void __launch_bounds__(TX_THREADS) k_split_offsets(const uint8_t *__restrict__ raw, const uint64_t *__restrict__ body_off, uint32_t nb, const uint8_t *__restrict__ status,
+                                                               const uint32_t *__restrict__ pay_beg, const uint32_t *__restrict__ pay_size, const uint32_t *__restrict__ first,
+                                                               const uint64_t *__restrict__ base, uint32_t n, uint64_t *__restrict__ off, uint32_t *__restrict__ dfirst,
+                                                               uint64_t *__restrict__ tx_beg, uint32_t *__restrict__ tx_size) {
+  const uint32_t b = blockIdx.x * TX_THREADS + threadIdx.x; if (b >= nb) return;
+  if (b == 0) { off[n] = base[nb]; if (dfirst) dfirst[nb] = n; }
+  if (dfirst) dfirst[b] = first[b];
+  if (status[b] != BODY_OK) return;
+  const uint64_t at = body_off[b], pk = base[b]; const uint8_t *t = raw + (at - body_off[0]); const uint32_t beg = pay_beg[b], e = beg + pay_size[b]; uint32_t p = beg, i = first[b];
+#pragma unroll 1
+  while (p < e && i < n) { const Head h = tx_head(t, p, e); if (h.bad) break;                        // (never: k_split_count accepted this head)
+    const uint32_t next = h.beg + h.size; off[i] = pk + (p - beg); tx_beg[i] = at + p; tx_size[i] = next - p; p = next; i++; }
+}
+// Packed word w holds the packed bytes 8w .. 8w + 7: byte d of the packed stream is byte d - base[b] of body b's item-0 payload, b the one body with base[b] <= d <
+// base[b+1], found by bisection (at most 32 turns; bodies without a payload share their base with the next and are never found).  A word takes at most eight pieces,
+// each from one or two aligned source words and a shift (raw starts at an aligned address and is padded to 8 bytes; the second word is read only where a wanted byte
+// lies in it, so the bytes shifted out lie inside the padded upload).  Bytes at and beyond the total are zero.  words = cdiv(total, 8).
+__global__ void __launch_bounds__(TX_THREADS) k_split_pack(const uint64_t *__restrict__ raw, const uint64_t *__restrict__ body_off, uint32_t nb, const uint32_t *__restrict__ pay_beg,
+                                                            const uint64_t *__restrict__ base, uint64_t total, uint64_t words, uint64_t *__restrict__ dst) {
+  const uint64_t w = (uint64_t)blockIdx.x * TX_THREADS + threadIdx.x; if (w >= words) return;
+  uint64_t d = 8 * w, val = 0; uint32_t filled = 0;
+#pragma unroll 1
+  for (int piece = 0; piece < 8 && filled < 8 && d < total; piece++) {
+    uint32_t b = 0, hi = nb;                                                                        // the largest b < nb with base[b] <= d; base[b+1] > d follows, base[nb] = total
+#pragma unroll 1
+    for (int it = 0; it < 32 && hi - b > 1; it++) { const uint32_t mid = b + ((hi - b) >> 1); if (base[mid] <= d) b = mid; else hi = mid; }
+    const uint64_t left = base[b + 1] - d, s = (body_off[b] - body_off[0]) + pay_beg[b] + (d - base[b]); const uint32_t take = left < 8u - filled ? (uint32_t)left : 8u - filled;   // 1 .. 8
+    const uint64_t k = s >> 3; const uint32_t r = (uint32_t)(s & 7u), shift = 8u * r; uint64_t v = raw[k] >> shift;
+    if (r + take > 8u) v |= raw[k + 1] << (64u - shift);                                           // (r > 0 here: the shift is below 64)
+    if (take < 8u) v &= (1ull << (8u * take)) - 1ull;
+    val |= v << (8u * filled); filled += take; d += take;
+  }
+  dst[w] = val;
+}
+
 // ---- the host side ------------------------------------------------------------------------------------------------------------------------------------------------
 namespace {
 struct Txs : PinnedStage {                           // one a process, every member under the device mutex
   DevBuf<uint32_t> io;
-  void grow(size_t words) { if (io.size() >= words) return; const size_t want = std::max(words, 2 * io.size()); io = DevBuf<uint32_t>(); io = DevBuf<uint32_t>(want); }   // (a failed growth leaves no workspace)
+  DevBuf<uint32_t> raw; PinnedStage raw_pin;          // the raw bodies' own buffer and pinned buffer (SplitLayout): live while the workspace is laid out and filled from them
+  static void grow(DevBuf<uint32_t> &b, size_t words) { if (b.size() >= words) return; const size_t want = std::max(words, 2 * b.size()); b = DevBuf<uint32_t>(); b = DevBuf<uint32_t>(want); }   // (a failed growth leaves no workspace)
+  void grow(size_t words) { grow(io, words); }
 };
 Txs &txs_state() { static Txs *t = new Txs; return *t; }   // (never destroyed: the runtime may be gone when statics are)
 static_assert(TXL_D_WORDS == TD_WORDS && TXL_E_WORDS == TE_WORDS && TXL_HEAD_WORDS == BH_WORDS && TXL_REC_WORDS == REC_WORDS && TXL_THREADS == TX_THREADS, "txs_layout.hpp carves for these kernels");
@@ -816,6 +911,12 @@ struct Staged {
     d.grow(L.end + TXL_SLACK); p = d.io.get(); if (!p) throw GpuError("txs: no workspace");
     dtx = (const uint8_t *)p; doff = (const uint64_t *)(p + L.off); dfirst = p + L.first;
     HIP_CHECK(hipMemcpyAsync(p, d.pin, L.up, hipMemcpyHostToDevice, s));
+  }
+  // the same without an upload: the split's launches fill the upload's place from the raw bodies (nothing of the workspace is live when it grows)
+  explicit Staged(const TxsUpload &L) : L(L) {
+    Txs &d = txs_state(); d.pinned(L.pin_bytes); back = d.pin + L.up;
+    d.grow(L.end + TXL_SLACK); p = d.io.get(); if (!p) throw GpuError("txs: no workspace");
+    dtx = (const uint8_t *)p; doff = (const uint64_t *)(p + L.off); dfirst = p + L.first;
   }
   uint32_t *dev(size_t x) const { return p + x; }
   uint8_t *host(size_t x) const { return back + 4 * (x - L.down); }
@@ -921,12 +1022,11 @@ size_t headers_decide(const HeadersIn &in, const HeadersOut &o) {
 // is queued and the launches are the ones zkTxRecords and verifyChainBodies have always made.
 static bool g_gather_bytewise = false;                                                              // (zkgpu_test_bodies_gather: the measurement of DESIGN.md §23; under the device mutex)
 void tx_records_gather_bytewise(bool on) { g_gather_bytewise = on; }
-size_t tx_records(const TxsIn &in, const BodyOut &o, size_t *first_bad, const int *borders, size_t n_borders, int *rec_borders, const RootsRequest *rq) {
+namespace {
+// the launches and the downloads of tx_records on a workspace whose upload's place is filled, or will be by what is queued on s: n > 0 transactions under L
+size_t records_on(const Staged &g, const RecordsLayout &L, const TxsIn &in, const BodyOut &o, size_t *first_bad, const int *borders, size_t n_borders, int *rec_borders, const RootsRequest *rq,
+                  hipStream_t s) {
   const size_t n = in.n, n_blocks = rq ? rq->n_lists : 0;
-  if (!n) { if (first_bad) *first_bad = 0; for (size_t k = 0; k < n_borders; k++) rec_borders[k] = 0; return 0; }
-  if (n > 0x3FFFFFFFu) throw GpuError("txs: more than 2^30 - 1 transactions");
-  LaneScope lane(0); hipStream_t s = gpu().stream; const RecordsLayout L = records_layout(n, (size_t)(in.off[n] - in.off[0]), n_blocks);
-  const Staged g(L, in.txs, in.off, n, rq ? rq->first : nullptr, s);
   uint32_t *D = g.dev(L.D), *E = g.dev(L.E), *hash = g.dev(L.hash), *rs = g.dev(L.rs), *xy = g.dev(L.xy), *v = g.dev(L.v), *rec = g.dev(L.rec), *src_of = g.dev(L.src_of), *counts = g.dev(L.counts), *bases = g.dev(L.bases);
   uint32_t *d_head = g.dev(L.head), *d_froms = g.dev(L.froms), *d_rec_froms = g.dev(L.rec_froms), *d_rec_of = g.dev(L.rec_of), *d_prefix = g.dev(L.prefix), *d_recs = g.dev(L.recs);
   const uint32_t *recovered = g.dev(L.recovered);
@@ -962,6 +1062,94 @@ size_t tx_records(const TxsIn &in, const BodyOut &o, size_t *first_bad, const in
   if (first_bad) *first_bad = head[BH_FIRST_BAD];
   return m;
 }
+}  // namespace
+size_t tx_records(const TxsIn &in, const BodyOut &o, size_t *first_bad, const int *borders, size_t n_borders, int *rec_borders, const RootsRequest *rq) {
+  const size_t n = in.n, n_blocks = rq ? rq->n_lists : 0;
+  if (!n) { if (first_bad) *first_bad = 0; for (size_t k = 0; k < n_borders; k++) rec_borders[k] = 0; return 0; }
+  if (n > 0x3FFFFFFFu) throw GpuError("txs: more than 2^30 - 1 transactions");
+  LaneScope lane(0); hipStream_t s = gpu().stream; const RecordsLayout L = records_layout(n, (size_t)(in.off[n] - in.off[0]), n_blocks);
+  const Staged g(L, in.txs, in.off, n, rq ? rq->first : nullptr, s);
+  return records_on(g, L, in, o, first_bad, borders, n_borders, rec_borders, rq, s);
+}
+// ---- zkBodySplit and verifyChainRawBodies (include/zk_raw_bodies.h) --------------------------------------------------------------------------------
+// The raw bodies cross the bus once, into Txs::raw.  split_count: the upload, k_split_count, k_split_scan, and the one mid-call synchronise that brings the head,
+// block_first and body_status down — the layout of everything behind depends on n and on the packed total, which the device alone knows.  split_fill: the two launches
+// that fill the upload's place of that layout from Txs::raw, queued in front of the launches that read it.
+namespace {
+static_assert(TXL_SPLIT_HEAD == SH_WORDS, "txs_layout.hpp carves for k_split_scan");
+struct SplitRun { SplitLayout L; uint32_t *r; uint8_t *back; size_t n, total, largest, k; };
+SplitRun split_count(const RawBodiesIn &in, const RawBodiesOut &o, bool write_unfit, hipStream_t s) {
+  const size_t nb = in.n_blocks;
+  if (nb > 0x3FFFFFFFu) throw GpuError("raw bodies: more than 2^30 - 1 bodies");
+  Txs &d = txs_state(); SplitRun R; R.L = split_layout(nb, (size_t)(in.body_off[nb] - in.body_off[0]), in.cap); const SplitLayout &L = R.L;
+  d.raw_pin.pinned(L.pin_bytes); uint8_t *pin = d.raw_pin.pin; R.back = pin + L.up;
+  if (L.total) memcpy(pin, in.bodies + in.body_off[0], L.total);
+  memset(pin + L.total, 0, L.total8 - L.total); memcpy(pin + L.total8, in.body_off, 8 * (nb + 1));
+  Txs::grow(d.raw, L.end + TXL_SLACK); uint32_t *r = R.r = d.raw.get(); if (!r) throw GpuError("raw bodies: no workspace");
+  HIP_CHECK(hipMemcpyAsync(r, pin, L.up, hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(k_split_count, dim3(cdiv(nb, TX_THREADS)), dim3(TX_THREADS), 0, s, (const uint8_t *)r, (const uint64_t *)(r + L.body_off), (uint32_t)nb, (uint8_t *)(r + L.status), r + L.count,
+                     r + L.pay_beg, r + L.pay_size);
+  hipLaunchKernelGGL(k_split_scan, dim3(1), dim3(SPLIT_SCAN_THREADS), 0, s, (const uint8_t *)(r + L.status), (const uint32_t *)(r + L.count), (const uint32_t *)(r + L.pay_size), (uint32_t)nb,
+                     r + L.first, (uint64_t *)(r + L.base), r + L.head);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipMemcpyAsync(R.back, r + L.down, 4 * (L.tx_beg - L.down), hipMemcpyDeviceToHost, s)); HIP_CHECK(hipStreamSynchronize(s));
+  uint32_t head[SH_WORDS]; memcpy(head, R.back, sizeof head);
+  const uint64_t n = (uint64_t)head[SH_N] | ((uint64_t)head[SH_N + 1] << 32), total = (uint64_t)head[SH_TOTAL] | ((uint64_t)head[SH_TOTAL + 1] << 32);
+  if (n > 0x3FFFFFFFu) throw GpuError("raw bodies: more than 2^30 - 1 transactions");
+  if (total > L.total || n > total || head[SH_LARGEST] > n || head[SH_K] > nb) throw GpuError("raw bodies: the counts left by the device are out of range");
+  R.n = (size_t)n; R.total = (size_t)total; R.largest = head[SH_LARGEST]; R.k = head[SH_K];
+  uint32_t last; memcpy(&last, R.back + 4 * (L.first + nb - L.down), 4);
+  if (last != R.n) throw GpuError("raw bodies: block_first does not end at the count left by the device");
+  if (R.n <= in.cap || write_unfit) { memcpy(o.block_first, R.back + 4 * (L.first - L.down), 4 * (nb + 1)); memcpy(o.body_status, R.back + 4 * (L.status - L.down), nb); }
+  return R;
+}
+// n <= tx_cap.  The downloads of tx_beg and tx_size are queued behind the launch that writes them; split_take copies them out once the stream has been synchronised.
+void split_fill(const SplitRun &R, const Staged &g, size_t nb, bool with_first, bool pack, hipStream_t s) {
+  const SplitLayout &L = R.L; uint32_t *r = R.r;
+  hipLaunchKernelGGL(k_split_offsets, dim3(cdiv(nb, TX_THREADS)), dim3(TX_THREADS), 0, s, (const uint8_t *)r, (const uint64_t *)(r + L.body_off), (uint32_t)nb, (const uint8_t *)(r + L.status),
+                     (const uint32_t *)(r + L.pay_beg), (const uint32_t *)(r + L.pay_size), (const uint32_t *)(r + L.first), (const uint64_t *)(r + L.base), (uint32_t)R.n, (uint64_t *)g.doff,
+                     with_first ? (uint32_t *)g.dfirst : (uint32_t *)nullptr, (uint64_t *)(r + L.tx_beg), r + L.tx_size);
+  const size_t words = (R.total + 7) / 8;
+  if (pack && words) hipLaunchKernelGGL(k_split_pack, dim3(cdiv(words, TX_THREADS)), dim3(TX_THREADS), 0, s, (const uint64_t *)r, (const uint64_t *)(r + L.body_off), (uint32_t)nb,
+                                        (const uint32_t *)(r + L.pay_beg), (const uint64_t *)(r + L.base), (uint64_t)R.total, (uint64_t)words, (uint64_t *)g.p);
+  HIP_CHECK(hipGetLastError());
+  if (R.n) { HIP_CHECK(hipMemcpyAsync(R.back + 4 * (L.tx_beg - L.down), r + L.tx_beg, 8 * R.n, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(R.back + 4 * (L.tx_size - L.down), r + L.tx_size, 4 * R.n, hipMemcpyDeviceToHost, s)); }
+}
+void split_take(const SplitRun &R, const RawBodiesOut &o) {
+  if (!R.n) return;
+  const SplitLayout &L = R.L; memcpy(o.tx_beg, R.back + 4 * (L.tx_beg - L.down), 8 * R.n); memcpy(o.tx_size, R.back + 4 * (L.tx_size - L.down), 4 * R.n);
+}
+}  // namespace
+// The callers have checked the arguments and hold the device mutex; n_blocks > 0.
+RawSplit body_split(const RawBodiesIn &in, const RawBodiesOut &o, uint8_t *packed, uint64_t *packed_off) {
+  LaneScope lane(0); hipStream_t s = gpu().stream; SyncAtExit sync;
+  const SplitRun R = split_count(in, o, true, s); const RawSplit out = {R.n, R.k, R.total, R.n <= in.cap};
+  if (!out.fits) return out;
+  const PackedLayout P = packed_layout(R.n, R.total, in.n_blocks); const Staged g(P);
+  split_fill(R, g, in.n_blocks, true, packed != nullptr, s);
+  if (packed) HIP_CHECK(hipMemcpyAsync(g.back, g.p, P.up, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s)); split_take(R, o);
+  if (packed) { if (R.total) memcpy(packed, g.back, R.total); memcpy(packed_off, g.back + 4 * P.off, 8 * (R.n + 1)); }
+  return out;
+}
+RawSplit raw_records(const RawBodiesIn &in, const RawBodiesOut &o, int signer, uint64_t chain_id, const BodyOut &bo, size_t *first_bad, int *rec_borders, uint8_t *roots, uint8_t *defined, size_t *m) {
+  LaneScope lane(0); hipStream_t s = gpu().stream; SyncAtExit sync; const size_t nb = in.n_blocks;
+  const SplitRun R = split_count(in, o, false, s); const RawSplit out = {R.n, R.k, R.total, R.n <= in.cap};
+  if (!out.fits) return out;
+  const RootsRequest rq = {o.block_first, nb, roots, defined};
+  if (!R.n) {                                                                                        // every body empty or refused: the roots of no transactions, as verifyChainBodiesRoots has them
+    const uint64_t off0[1] = {0}; trie_roots(nullptr, off0, 0, rq, true);
+    *first_bad = 0; *m = 0; for (size_t b = 0; b <= nb; b++) rec_borders[b] = 0;
+    return out; }
+  const RecordsLayout L = records_layout(R.n, R.total, nb); const Staged g(L);
+  split_fill(R, g, nb, true, true, s);
+  const TxsIn tin = {nullptr, nullptr, R.n, signer, chain_id};                                      // (the bytes and off are the device's)
+  *m = records_on(g, L, tin, bo, first_bad, o.block_first, nb + 1, rec_borders, &rq, s);             // (synchronises: tx_beg and tx_size have landed)
+  split_take(R, o);
+  return out;
+}
+
 // Keccak-256 of n byte strings, msgs[off[i] .. off[i+1]), through k_tx_hash's sponge
 void probe_keccak256(const uint8_t *msgs, const uint64_t *off, size_t n, uint8_t *out) {
   if (!n) return;

@@ -8,6 +8,7 @@
 #include "../../include/zk_records.h"
 #include "../../include/zk_txs.h"
 #include "../../include/zk_headers.h"
+#include "../../include/zk_raw_bodies.h"
 #include "gpu.hpp"
 #include "txs_layout.hpp"
 
@@ -33,6 +34,23 @@ size_t tx_sender_inputs(const TxsIn &in, bool want_senders, const SenderInputsOu
 size_t tx_records(const TxsIn &in, const BodyOut &o, size_t *first_bad, const int *borders, size_t n_borders, int *rec_borders, const RootsRequest *roots);
 size_t headers_decide(const HeadersIn &in, const HeadersOut &o);
 size_t trie_roots(const uint8_t *vals, const uint64_t *off, size_t n, const RootsRequest &rq, bool want_tx);
+// zkBodySplit and verifyChainRawBodies (include/zk_raw_bodies.h): n_blocks > 0 bodies, bodies[body_off[b] .. body_off[b+1]); tx_beg and tx_size have room for cap,
+// block_first for n_blocks + 1, body_status for n_blocks.  What the split found: n transactions, k leading bodies that are OK, the packed bytes; fits: n <= cap —
+// without it block_first and body_status alone are written (body_split) or nothing at all (raw_records), and nothing else is queued.
+struct RawBodiesIn { const uint8_t *bodies; const uint64_t *body_off; size_t n_blocks, cap; };
+struct RawBodiesOut { uint64_t *tx_beg; uint32_t *tx_size; int *block_first; uint8_t *body_status; };
+struct RawSplit { size_t n, k, total; bool fits; };
+// packed (may be null; the test entry): the packed bytes, room for body_off[n_blocks] - body_off[0], and packed_off, cap + 1 values
+RawSplit body_split(const RawBodiesIn &in, const RawBodiesOut &o, uint8_t *packed, uint64_t *packed_off);
+// the split, then tx_records on what it packed with the blocks' roots (roots, defined: n_blocks each); rec_borders: n_blocks + 1; *m: the records
+RawSplit raw_records(const RawBodiesIn &in, const RawBodiesOut &o, int signer, uint64_t chain_id, const BodyOut &bo, size_t *first_bad, int *rec_borders, uint8_t *roots, uint8_t *defined, size_t *m);
+// capi_bodies.cpp: the chain call on the bodies' bytes in its three forms.  raw (verifyChainRawBodies; null for the other two): the bodies as they were delivered and
+// what the split leaves; n is then the caller's cap, and txs, off and block_first are null.
+struct RawChain { const uint8_t *bodies; const uint64_t *body_off; int cap; uint64_t *tx_beg; uint32_t *tx_size; int *block_first; uint8_t *body_status; int *n_txs; };
+int chain_bodies(const char *name, bool with_roots, zk_proof_cache *cache, const uint8_t *txs, const uint64_t *off, int n, const int *block_first, int n_blocks, int signer, uint64_t chain_id,
+                 zk_accts *accts, zk_tree *tree, const long long *prior_anchors, int n_prior, int window, zk_snset *set, zk_block_record *recs, uint8_t (*rec_froms)[20], int32_t *rec_of,
+                 uint8_t (*txhash)[32], uint8_t (*froms)[20], uint8_t *code, uint8_t *status, unsigned char *ok, int32_t *anchor_of, long long *accts_sizes, long long *set_sizes,
+                 long long *tree_sizes, int *n_recs, const uint8_t (*want_roots)[32], uint8_t (*roots)[32], unsigned char *root_ok, const RawChain *raw);
 void probe_keccak256(const uint8_t *msgs, const uint64_t *off, size_t n, uint8_t *out);
 void tx_records_gather_bytewise(bool on);
 // gpu_senders.hip

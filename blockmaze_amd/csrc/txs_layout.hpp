@@ -123,4 +123,33 @@ inline KeccakLayout keccak_layout(size_t n, size_t total_bytes) {
   L.down = L.out = c.take(8 * n); L.down_end = L.end = c.at; L.pin_bytes = L.up + 4 * (L.down_end - L.down); return L;
 }
 
+// zkBodySplit and verifyChainRawBodies (include/zk_raw_bodies.h).  The raw bodies have a buffer and a pinned buffer of their own, kept beside the
+// workspace: the bodies' bytes go up here, and what the split packs from them fills the upload's place of a layout above, as if the caller had supplied it.
+// Device, in words: up (the bytes body_off[0] .. body_off[n_blocks), padded to 8 | body_off, n_blocks + 1 64-bit values) | pay_beg n_blocks | pay_size n_blocks |
+// count n_blocks | base, n_blocks + 1 64-bit values | down.
+// Down, in words: head 8 (n, 64 bits | the packed total, 64 bits | the largest block | the first body that is not OK | -, -) | first n_blocks + 1 | status, n_blocks
+// bytes | tx_beg, tx_cap 64-bit values | tx_size tx_cap.  head .. tx_beg comes down at the mid-call synchronise, the first n entries of tx_beg and of tx_size behind the
+// launches that wrote them.  tx_cap: the caller's cap, or the number of bytes where that is less — an element has at least one byte.
+constexpr size_t TXL_SPLIT_HEAD = 8;
+struct SplitLayout {
+  size_t total, total8, up;                              // bytes: the caller's, those padded to 8, the whole upload
+  size_t body_off, pay_beg, pay_size, count, base, head, first, status, tx_beg, tx_size, tx_cap;   // words (tx_cap: entries)
+  size_t down, end, pin_bytes;
+};
+inline SplitLayout split_layout(size_t n_blocks, size_t total_bytes, size_t cap) {
+  SplitLayout L; Carve c; L.total = total_bytes; L.tx_cap = cap < total_bytes ? cap : total_bytes;
+  c.take(Carve::bytes(L.total));                         // (k_split_pack reads these as aligned 64-bit words, the padding included)
+  L.body_off = c.take(2 * (n_blocks + 1), 2); L.up = 4 * c.at; L.total8 = 4 * L.body_off;
+  L.pay_beg = c.take(n_blocks); L.pay_size = c.take(n_blocks); L.count = c.take(n_blocks); L.base = c.take(2 * (n_blocks + 1), 2);
+  L.down = L.head = c.take(TXL_SPLIT_HEAD, 2); L.first = c.take(n_blocks + 1); L.status = c.take(Carve::bytes(n_blocks));
+  L.tx_beg = c.take(2 * L.tx_cap, 2); L.tx_size = c.take(L.tx_cap); L.end = c.take(0, 2); L.pin_bytes = L.up + 4 * (L.end - L.down);
+  return L;
+}
+// what zkBodySplit alone packs into: the upload's place and nothing behind it; the test entry brings it down again whole
+struct PackedLayout : TxsUpload {};
+inline PackedLayout packed_layout(size_t n, size_t total_bytes, size_t n_blocks) {
+  PackedLayout L; Carve c = carve_upload(L, n, total_bytes, n_blocks + 1);
+  L.down = 0; L.down_end = L.end = c.at; L.pin_bytes = 2 * L.up; return L;
+}
+
 }  // namespace zk

@@ -181,6 +181,29 @@ def headers(hdrs, period, epoch, now, parent, fill=0xA5, start=0):
     buffer (off[0] = start)"""
     f = lib().zkgpu_headers; f.restype = ctypes.c_int; return _headers_call(f, hdrs, period, epoch, now, parent, fill, start)
 
+# block bodies from their bytes (csrc/gpu_txs.hip, csrc/capi_raw_bodies.cpp; include/zk_raw_bodies.h)
+BODY_OK, BODY_MALFORMED, BODY_UNCLES = 0, 1, 2
+ERR_CAP = -5
+def _body_blob(bodies, start=0):
+    """_tx_blob with `start` bytes in front: the blob begins at that byte of its buffer (body_off[0] = start)"""
+    blob, off = _tx_blob(bodies)
+    if start: blob = np.concatenate([np.full(start, 0xEE, dtype=np.uint8), blob]); off = off + np.uint64(start)
+    return blob, off
+def body_split(bodies, cap=None, start=0, packed=False, fill=0xA5):
+    """zkgpu_body_split (packed: zkgpu_test_body_split) -> (k, ERR_CAP or a ZKGPU_ERR_* code, dict of n_txs, tx_beg (cap,) uint64, tx_size (cap,) uint32, block_first
+    (n_blocks + 1,) int32, body_status (n_blocks,) uint8 and, with packed, packed: the bytes where the kernels read txs, cut at off[n], packed_off (cap + 1,) uint64);
+    every array is handed in full of `fill` bytes.  cap None: room for one transaction a byte"""
+    nb = len(bodies); blob, off = _body_blob(bodies, start); total = int(off[nb] - off[0]); cap = total if cap is None else int(cap)
+    mk = lambda count, dt: np.frombuffer(bytes([fill]) * (np.dtype(dt).itemsize * max(1, count)), dtype=dt).copy()
+    o = dict(tx_beg=mk(cap, np.uint64), tx_size=mk(cap, np.uint32), block_first=mk(nb + 1, np.int32), body_status=mk(nb, np.uint8)); n = ctypes.c_int(-7); vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    args = [_bytes(blob), _u64p(off), nb, cap, vp(o["tx_beg"]), vp(o["tx_size"]), vp(o["block_first"]), vp(o["body_status"]), ctypes.byref(n)]
+    if packed:
+        pk, po = mk(total, np.uint8), mk(cap + 1, np.uint64); f = lib().zkgpu_test_body_split; f.restype = ctypes.c_int; rc = int(f(*args, vp(pk), vp(po)))
+        o["packed_off"] = po[:cap + 1]; o["packed"] = bytes(pk[:int(po[n.value])]) if rc >= 0 else bytes(pk[:total])
+    else: f = lib().zkgpu_body_split; f.restype = ctypes.c_int; rc = int(f(*args))
+    o["n_txs"] = int(n.value); o["tx_beg"] = o["tx_beg"][:cap]; o["tx_size"] = o["tx_size"][:cap]; o["body_status"] = o["body_status"][:nb]
+    return rc, o
+
 def msm(group, points, scalars, window_bits=0, filter_ones=False):
     points = np.ascontiguousarray(points, dtype=np.uint64); scalars = np.ascontiguousarray(scalars, dtype=np.uint64); n = scalars.size // 4
     out = np.zeros(8 if group == 1 else 16, dtype=np.uint64)
@@ -1005,6 +1028,39 @@ class Zk:
                         anchor_of=[int(an[j]) for j in range(k)], accts_sizes=out[0], set_sizes=(out[1] if s else None), tree_sizes=out[2],
                         roots=[bytes(roots[b]) for b in range(max(0, nb))], root_ok=[bool(rok[b]) for b in range(max(0, nb))],
                         raw=dict(recs=recs, rec_froms=rf, rec_of=of, txhash=th, froms=fr, code=code, status=st, ok=ok, anchor_of=an, roots=roots, root_ok=rok))
+    # include/zk_raw_bodies.h: the bodies as a peer or the database delivered them, one offset a block
+    def BodySplit(self, bodies, cap=None, start=0):
+        """bodies: n_blocks byte strings, rlp([[tx ...], [uncle ...]]) each.  -> (k: the leading bodies with status BODY_OK, or -2 where cap is too small, and a dict: n_txs,
+        block_first: [int] x (n_blocks + 1), body_status: [int], tx_beg, tx_size: [int] x n_txs (empty with -2)); raises ZkGpuError where the call returns -1"""
+        nb = len(bodies); blob, off = _body_blob(bodies, start); cap = int(off[nb] - off[0]) if cap is None else int(cap)
+        tb = np.zeros(max(1, cap), dtype=np.uint64); ts = np.zeros(max(1, cap), dtype=np.uint32); bf = np.zeros(nb + 1, dtype=np.int32); st = np.zeros(max(1, nb), dtype=np.uint8); n = ctypes.c_int(0)
+        vp = lambda x: x.ctypes.data_as(ctypes.c_void_p); self.L.zkBodySplit.restype = ctypes.c_int
+        k = int(self.L.zkBodySplit(_bytes(blob), _u64p(off), nb, cap, vp(tb), vp(ts), vp(bf), vp(st), ctypes.byref(n)))
+        if k == -1: raise ZkGpuError("zkBodySplit: %s" % self.L.zkgpu_last_error().decode())
+        m = int(n.value) if k >= 0 else 0
+        return k, dict(n_txs=int(n.value), block_first=[int(x) for x in bf], body_status=[int(x) for x in st[:nb]], tx_beg=[int(x) for x in tb[:m]], tx_size=[int(x) for x in ts[:m]])
+    def VerifyChainRawBodies(self, cache, bodies, want_roots, signer, chain_id, a, tree, prior_anchors, window, s, cap=None, fill=0, start=0):
+        """VerifyChainBodiesRoots on the bodies' bytes: no txs, no block_first.  -> (blocks accepted, -1 or -2, VerifyChainBodiesRoots' dict over the n_txs transactions
+        the split found, and n_txs, block_first, body_status, tx_beg, tx_size); cap None: room for one transaction a byte"""
+        nb = len(bodies); blob, off = _body_blob(bodies, start); cap = int(off[nb] - off[0]) if cap is None else int(cap); c1 = max(1, cap)
+        pa = np.ascontiguousarray(prior_anchors if prior_anchors is not None else [], dtype=np.int64).reshape(-1); npa = int(pa.size)
+        recs = np.frombuffer(bytes([fill]) * (720 * c1), dtype=RECORD_DTYPE).copy(); rf, th, fr, code, st, ok = [np.full((c1, w), fill, dtype=np.uint8) for w in (20, 32, 20, 1, 1, 1)]
+        of = np.full(c1, -7, dtype=np.int32); an = np.full(c1, -7, dtype=np.int32); sizes = [np.full(max(1, nb), -7, dtype=np.int64) for _ in range(3)]; m = ctypes.c_int(-7)
+        want = np.frombuffer(b"".join(bytes(r) for r in want_roots) or bytes(32), dtype=np.uint8).copy(); roots = np.full((max(1, nb), 32), fill, dtype=np.uint8); rok = np.full(max(1, nb), fill, dtype=np.uint8)
+        tb = np.frombuffer(bytes([fill]) * (8 * c1), dtype=np.uint64).copy(); ts = np.frombuffer(bytes([fill]) * (4 * c1), dtype=np.uint32).copy(); bf = np.frombuffer(bytes([fill]) * (4 * (nb + 1)), dtype=np.int32).copy()
+        bs = np.full(max(1, nb), fill, dtype=np.uint8); nt = ctypes.c_int(-7)
+        vp = lambda x: x.ctypes.data_as(ctypes.c_void_p); self.L.verifyChainRawBodies.restype = ctypes.c_int
+        rc = int(self.L.verifyChainRawBodies(_cache_handle(cache), _bytes(blob), _u64p(off), nb, cap, int(signer), ctypes.c_uint64(chain_id), _accts_handle(a), ctypes.c_void_p(tree) if tree else None,
+                                             vp(pa) if npa else None, npa, int(window), ctypes.c_void_p(s) if s else None, vp(recs), vp(rf), vp(of), vp(th), vp(fr), vp(code), vp(st), vp(ok), vp(an),
+                                             *[vp(x) for x in sizes], ctypes.byref(m), vp(want), vp(roots), vp(rok), vp(tb), vp(ts), vp(bf), vp(bs), ctypes.byref(nt)))
+        n = max(0, int(nt.value)) if rc >= 0 else 0; k = max(0, int(m.value)); out = [[int(x) for x in v[:nb]] if rc >= 0 else None for v in sizes]
+        return rc, dict(n_recs=int(m.value), recs=recs[:k].copy(), rec_froms=[bytes(rf[j]) for j in range(k)], rec_of=[int(of[i]) for i in range(n)], froms=[bytes(fr[i]) for i in range(n)],
+                        txhash=[bytes(th[i]) for i in range(n)], code=[int(code[i, 0]) for i in range(n)], status=[int(st[i, 0]) for i in range(n)], ok=[bool(ok[j, 0]) for j in range(k)],
+                        anchor_of=[int(an[j]) for j in range(k)], accts_sizes=out[0], set_sizes=(out[1] if s else None), tree_sizes=out[2],
+                        roots=[bytes(roots[b]) for b in range(nb)], root_ok=[bool(rok[b]) for b in range(nb)], n_txs=int(nt.value), block_first=[int(x) for x in bf],
+                        body_status=[int(x) for x in bs[:nb]], tx_beg=[int(x) for x in tb[:n]], tx_size=[int(x) for x in ts[:n]],
+                        raw=dict(recs=recs, rec_froms=rf, rec_of=of, txhash=th, froms=fr, code=code, status=st, ok=ok, anchor_of=an, roots=roots, root_ok=rok, tx_beg=tb, tx_size=ts, block_first=bf,
+                                 body_status=bs))
     # include/zk_headers.h: a batch of headers decided from their bytes; tx_root goes into VerifyChainBodiesRoots as want_roots
     def Headers(self, hdrs, period, epoch, now, parent):
         """hdrs: n byte strings, one RLP header each; parent: None or (hash, number, time) of the parent of header 0.  -> (k, the leading headers with status HDR_OK, and a

@@ -39,8 +39,8 @@
  * digit, so such a record is rejected by the proof step.
  *
  * Not here: records handed to the chain call without the trip through recs; DepositTxV/R/S (no reference code path reads them
- * on import); a pool form; a miner's drop-and-go-on; streaming a body's outer list; nonce, balance and gas rules of public transactions; any change to the recovery
- * or to verifyChainAccounts.
+ * on import); a pool form; a miner's drop-and-go-on; nonce, balance and gas rules of public transactions; any change to the recovery or to verifyChainAccounts.  (A
+ * body's outer list: zk_raw_bodies.h.)
  *
  * May be called from any thread; calls are served one at a time.  Exported by libzkgpu.so only: a caller that wants it adds -lzkgpu to its link line.
  */

@@ -470,6 +470,22 @@ int zkgpu_headers(const uint8_t *hdrs, const uint64_t *off /* n + 1 */, int n, u
                   uint8_t *tx_root /* n x 32 */, uint8_t *rtcmt /* n x 32 */, uint64_t *number, uint64_t *time, uint8_t *difficulty, uint8_t *vote, uint32_t *extra_beg,
                   uint32_t *extra_size, uint32_t *cmt_beg, uint32_t *cmt_count, uint8_t *status);
 
+/* ---- block bodies from their bytes (the drop-in level is zk_raw_bodies.h) -----------------------------------------------------------------------
+ * The bodies rlp([[tx ...], [uncle ...]]) go up once.  k_split_count, a lane a body, decides the outer list, the two lists in it and every element head of the first
+ * with the walk's own head reader; k_split_scan scans the element counts and the payload sizes over the blocks; one synchronise brings n, the packed total and
+ * block_first down, and the host lays the workspace out for them; k_split_offsets walks again and writes off, tx_beg and tx_size; k_split_pack copies the payloads of
+ * the OK bodies end to end, a lane an aligned 8-byte word, to where every kernel of the transaction calls reads txs.
+ * Takes the arguments of zkBodySplit and returns k, the number of leading bodies with status ZK_BODY_OK; ZKGPU_ERR_CAP (zkBodySplit's -2: n > cap; *n_txs,
+ * block_first and body_status are valid, tx_beg and tx_size zeroed); or ZKGPU_ERR_ARG (a negative count, a null pointer with n_blocks > 0, a decreasing body_off; decided
+ * first, before the device is asked for), ZKGPU_ERR_NO_DEVICE, ZKGPU_ERR_RUNTIME, every output zeroed on each of the three. */
+#define ZKGPU_ERR_CAP (-5)
+int zkgpu_body_split(const uint8_t *bodies, const uint64_t *body_off /* n_blocks + 1 */, int n_blocks, int cap, uint64_t *tx_beg /* cap */, uint32_t *tx_size /* cap */,
+                     int *block_first /* n_blocks + 1 */, uint8_t *body_status /* n_blocks */, int *n_txs);
+/* test entry: zkgpu_body_split, and what k_split_offsets and k_split_pack left where the kernels read txs and off: packed, room for body_off[n_blocks] - body_off[0]
+ * bytes, of which the packed total is written, and packed_off, cap + 1 values of which n + 1 are written; both zeroed where the call does not return k */
+int zkgpu_test_body_split(const uint8_t *bodies, const uint64_t *body_off, int n_blocks, int cap, uint64_t *tx_beg, uint32_t *tx_size, int *block_first, uint8_t *body_status, int *n_txs,
+                          uint8_t *packed, uint64_t *packed_off);
+
 #ifdef __cplusplus
 }
 #endif
