@@ -10,20 +10,20 @@ DEPOSIT_KEY = 4                                                 # zk_bodies.h: Z
 KIND_OF_CODE = {1: 0, 2: 1, 3: 2, 5: 3}                         # transaction.go:40-46 MintTx, SendTx, DepositTx, RedeemTx -> zk_batch.h ZK_KIND_*; state_processor.go:108-164 has no branch for 0, 4, > 5
 ZERO32 = bytes(32)
 
-def six_field_hash(tx):
+def six_field_hash(tx, keccak=t.keccak256):
     """HomesteadSigner's hash = FrontierSigner's (transaction_signing.go:231-240): never the nine-field one"""
-    return t.sig_hash(dict(tx, V=27), t.HOMESTEAD, 0)
-def deposit_key(tx):
+    return t.sig_hash(dict(tx, V=27), t.HOMESTEAD, 0, keccak)
+def deposit_key(tx, keccak=t.keccak256):
     """state_processor.go:141-146 for a decoded deposit -> (accepted, addr1).  addr1 = ExtractPKBAddress(HomesteadSigner{}, tx) (transaction_signing.go:96-113 ->
     :206-208 -> recoverPlain :246-271 with homestead = true); addr2 = PubkeyToAddress({X, Y}) (crypto.go:212-215)"""
     v, r, s, x, y = tx["V"], tx["R"], tx["S"], tx["X"], tx["Y"]
     if v.bit_length() > 8: return False, bytes(20)                                          # :247
     vb = (v - 27) & 0xFF                                                                     # :250, no chain-id arithmetic: 37 gives 10
     if r.bit_length() > 256 or s.bit_length() > 256: return False, bytes(20)                # :255-258 cannot hold them (ValidateSignatureValues, crypto.go:209, refuses them first: r, s < N)
-    ok, _, _, addr1 = sm.recover(six_field_hash(tx), r.to_bytes(32, "big") + s.to_bytes(32, "big") + bytes([vb]), True)   # :251 homestead = true whatever the block's signer
+    ok, _, _, addr1 = sm.recover(six_field_hash(tx, keccak), r.to_bytes(32, "big") + s.to_bytes(32, "big") + bytes([vb]), True)   # :251 homestead = true whatever the block's signer
     if not ok: return False, bytes(20)                                                       # state_processor.go:144 err != nil
     if x.bit_length() > 256 or y.bit_length() > 256: return False, bytes(20)                # crypto.go:136-141: elliptic.Marshal slices out of range, the node dies; zk_bodies.h refuses
-    addr2 = t.keccak256(x.to_bytes(32, "big") + y.to_bytes(32, "big"))[12:]                 # crypto.go:212-215; no curve check
+    addr2 = keccak(x.to_bytes(32, "big") + y.to_bytes(32, "big"))[12:]                 # crypto.go:212-215; no curve check
     return addr1 == addr2, addr1                                                             # state_processor.go:144 addr1 != addr2
 
 def record_bytes(tx, pk=None):
@@ -36,23 +36,23 @@ def record_bytes(tx, pk=None):
     return struct.pack("<B7xQ", kind, value) + proof + b"".join(args).ljust(192, b"\0")
 
 _memo = {}
-def one(raw, signer, chain_id):
+def one(raw, signer, chain_id, keccak=t.keccak256):
     """zkTxRecords for one transaction -> (status, code, txhash, from, the record's 720 bytes or None)"""
-    key = (bytes(raw), signer, chain_id)
+    key = (bytes(raw), signer, chain_id, keccak)
     if key in _memo: return _memo[key]
-    status, code, txhash, frm = t.sender(raw, signer, chain_id); rec = None
+    status, code, txhash, frm = t.sender(raw, signer, chain_id, keccak); rec = None
     if status != t.MALFORMED and code == t.DEPOSIT:                                          # (Sender never fails for a decoded deposit: transaction_signing.go:72-76)
-        tx, _ = t.decode(raw); good, pk = deposit_key(tx)
+        tx, _ = t.decode(raw); good, pk = deposit_key(tx, keccak)
         if good: rec = record_bytes(tx, pk)
         else: status, frm = DEPOSIT_KEY, bytes(20)
     elif status == t.OK and code in KIND_OF_CODE: rec = record_bytes(t.decode(raw)[0])
     _memo[key] = (status, code, txhash, frm, rec); return _memo[key]
 
-def records(raws, signer, chain_id):
+def records(raws, signer, chain_id, keccak=t.keccak256):
     """zkTxRecords -> (recs: [720 bytes] x m, rec_froms: [20 bytes] x m, rec_of: [int] x n, froms, code, status, txhash)"""
     recs, rec_froms, rec_of, froms, code, status, txhash = [], [], [], [], [], [], []
     for raw in raws:
-        st, c, th, frm, rec = one(raw, signer, chain_id); froms.append(frm); code.append(c); status.append(st); txhash.append(th)
+        st, c, th, frm, rec = one(raw, signer, chain_id, keccak); froms.append(frm); code.append(c); status.append(st); txhash.append(th)
         if rec is None: rec_of.append(-1)
         else: rec_of.append(len(recs)); recs.append(rec); rec_froms.append(frm)
     return recs, rec_froms, rec_of, froms, code, status, txhash

@@ -73,10 +73,10 @@ def decode(raw):
     if pos != lim: raise t.Malformed("too many elements")                                      # :449, :778
     return h, spans, contents
 
-def header_hash(h): return t.keccak256(encode(h))                                              # block.go:105-107: all 17 fields
-def seal_hash(h, cut=SEAL_BYTES):
+def header_hash(h, keccak=t.keccak256): return keccak(encode(h))                                              # block.go:105-107: all 17 fields
+def seal_hash(h, cut=SEAL_BYTES, keccak=t.keccak256):
     """clique.go:147-169: the upstream 15 fields, Extra without its last `cut` bytes"""
-    assert len(h["Extra"]) >= cut; items = encode_items(h, SEAL_FIELDS); items[I_EXTRA] = t.enc_str(h["Extra"][:len(h["Extra"]) - cut]); return t.keccak256(t.enc_list(items))
+    assert len(h["Extra"]) >= cut; items = encode_items(h, SEAL_FIELDS); items[I_EXTRA] = t.enc_str(h["Extra"][:len(h["Extra"]) - cut]); return keccak(t.enc_list(items))
 
 def seal_recover(sighash, sig):
     """crypto.Ecrecover(sighash, sig) as ecrecover calls it (clique.go:185) -> (OK, signer) | (SEAL, None) | (SEAL_UNDECIDED, None).  No ValidateSignatureValues, no low-s
@@ -112,14 +112,15 @@ def standalone(h, epoch, now):
     if h["UncleHash"] != UNCLE_HASH_EMPTY: return UNCLE_HASH                                   # :311
     if number > 0 and h["Difficulty"] not in (1, 2): return DIFFICULTY                         # :315-318
     return OK
-def headers(raws, period, epoch, now, parent):
+def headers(raws, period, epoch, now, parent, keccak=t.keccak256):
     """zkHeaders -> a dict of the header's outputs per header.  parent: None (have_parent = 0) or (hash, number, time) of the parent of header 0 as the caller found it.
-    Every header is decided against its predecessor in the batch whatever that predecessor's status (clique.go:253 passes headers[:i])."""
-    epoch = epoch or EPOCH; out = []; prev = parent
+    Every header is decided against its predecessor in the batch whatever that predecessor's status (clique.go:253 passes headers[:i]).  keccak: the hash function, as
+    trie_model.derive_sha takes one; what is remembered of a header is remembered for each function apart."""
+    epoch = epoch or EPOCH; out = []; prev = parent; _DECODED = _DECODED_BY.setdefault(keccak, {})
     for raw in raws:
         raw = bytes(raw)
         if raw not in _DECODED:                                                                # (the decoder and the two hashes once a distinct header, as for the seals)
-            try: h, spans, contents = decode(raw); _DECODED[raw] = (h, contents, header_hash(h), seal_hash(h) if len(h["Extra"]) >= SEAL_BYTES else bytes(32))
+            try: h, spans, contents = decode(raw); _DECODED[raw] = (h, contents, header_hash(h, keccak), seal_hash(h, keccak=keccak) if len(h["Extra"]) >= SEAL_BYTES else bytes(32))
             except t.Malformed: _DECODED[raw] = None
             assert _DECODED[raw] is None or encode(h) == raw                                   # the strict decoder: the re-encoding is the input
         if _DECODED[raw] is None: out.append(dict(ZERO)); prev = None; continue               # (a header behind one that does not decode has no parent: ANCESTOR)
@@ -136,7 +137,7 @@ def headers(raws, period, epoch, now, parent):
                 if status == OK: o["signer"] = signer
         o["status"] = status; out.append(o); prev = (hh, number, h["Time"] & M64)
     return out
-_DECODED = {}
+_DECODED_BY = {}
 def accepted(outs):
     k = 0
     while k < len(outs) and outs[k]["status"] == OK: k += 1

@@ -124,13 +124,14 @@ def is_protected(v): return v not in (27, 28) if v.bit_length() <= 8 else True  
 def derive_chain_id(v):                                                                      # transaction_signing.go:274-284
     if v.bit_length() <= 64: return 0 if v in (27, 28) else ((v - 35) & M64) // 2            # uint64 arithmetic: below 35 it wraps
     return (v - 35) // 2
-def sig_hash(tx, signer, chain_id):
+def sig_hash(tx, signer, chain_id, keccak=keccak256):
     six = [enc_int(tx["AccountNonce"]), enc_int(tx["Price"]), enc_int(tx["GasLimit"]), b"\x80" if tx["Recipient"] is None else enc_str(tx["Recipient"]), enc_int(tx["Amount"]),
            enc_str(tx["Payload"])]
     if signer == EIP155 and is_protected(tx["V"]): six += [enc_int(chain_id), b"\x80", b"\x80"]   # :179-189; an unprotected V takes Homestead's road, :152-154
-    return keccak256(enc_list(six))
-def signing_inputs(raw, signer, chain_id):
-    """zkTxSigningInputs for one transaction -> dict(status, code, txhash, sighash, sig, deposit_from): the header's outputs"""
+    return keccak(enc_list(six))
+def signing_inputs(raw, signer, chain_id, keccak=keccak256):
+    """zkTxSigningInputs for one transaction -> dict(status, code, txhash, sighash, sig, deposit_from): the header's outputs; keccak: the hash function, as
+    trie_model.derive_sha takes one"""
     zero = dict(status=MALFORMED, code=0, txhash=bytes(32), sighash=bytes(32), sig=bytes(65), deposit_from=bytes(20))
     try: tx, spans = decode(raw)
     except Malformed: return zero
@@ -145,10 +146,10 @@ def signing_inputs(raw, signer, chain_id):
         sig = (r.to_bytes(32, "big") if r.bit_length() <= 256 else bytes(32)) + (s.to_bytes(32, "big") if s.bit_length() <= 256 else bytes(32)) + bytes([vbyte if (status == OK or (status == SIG and vs.bit_length() <= 8)) else 0])
         status = OK
     else: sig = r.to_bytes(32, "big") + s.to_bytes(32, "big") + bytes([vbyte]) if status == OK else bytes(65)
-    return dict(status=status, code=code, txhash=keccak256(reenc), sighash=sig_hash(tx, signer, chain_id), sig=sig, deposit_from=tx["ZKAdrress"] if code == DEPOSIT else bytes(20))
-def sender(raw, signer, chain_id):
+    return dict(status=status, code=code, txhash=keccak(reenc), sighash=sig_hash(tx, signer, chain_id, keccak), sig=sig, deposit_from=tx["ZKAdrress"] if code == DEPOSIT else bytes(20))
+def sender(raw, signer, chain_id, keccak=keccak256):
     """zkTxSenders for one transaction -> (status, code, txhash, from): types.Sender(signer, tx) after the decode"""
-    d = signing_inputs(raw, signer, chain_id)
+    d = signing_inputs(raw, signer, chain_id, keccak)
     if d["status"] != OK: return d["status"], d["code"], d["txhash"], bytes(20)
     if d["code"] == DEPOSIT: return OK, d["code"], d["txhash"], d["deposit_from"]
     ok, _, _, addr = sm.recover(d["sighash"], d["sig"], signer != FRONTIER)
