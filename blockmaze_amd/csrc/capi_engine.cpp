@@ -129,7 +129,50 @@ int zkgpu_test_msm_run_product(zkgpu_msm *h, const uint8_t *a, const uint8_t *b,
 int zkgpu_test_msm_h_state(zkgpu_msm *h, int what, uint32_t *out, size_t cap_words, size_t *words) {
   return guarded([&] { if (!h || h->group != 1 || !out || !words) { g_err = "a G1 MSM object"; return ZKGPU_ERR_ARG; }
     *words = h->g1->test_h_state(what, out, cap_words); return ZKGPU_OK; }); }
-static int msm_oneshot(int group, const uint8_t *points, const uint8_t *scalars, size_t n, int c, int fo, uint8_t *out) {
+// test entry points of the three-launch witness path, both groups (gpu.hpp: MSM_WPATH_WORDS; msm_impl.hpp: test_wpath / test_w_state), and the ways the prover drives it
+int zkgpu_test_msm_wpath(zkgpu_msm *h, uint32_t out[20]) { return guarded([&] { if (!h || !out) { g_err = "an MSM object"; return ZKGPU_ERR_ARG; }
+  static_assert(MSM_WPATH_WORDS == 20, "zkgpu.h says 20 words"); if (h->group == 1) h->g1->test_wpath(out); else h->g2->test_wpath(out); return ZKGPU_OK; }); }
+int zkgpu_test_msm_w_state(zkgpu_msm *h, int what, uint32_t *out, size_t cap_words, size_t *words) {
+  return guarded([&] { if (!h || !out || !words) { g_err = "an MSM object"; return ZKGPU_ERR_ARG; }
+    *words = h->group == 1 ? h->g1->test_w_state(what, out, cap_words) : h->g2->test_w_state(what, out, cap_words); return ZKGPU_OK; }); }
+int zkgpu_test_msm_share_sort(zkgpu_msm *follower, zkgpu_msm *leader) {   // 1 accepted, 0 refused
+  return guarded([&] { if (!follower || !leader || follower == leader) { g_err = "two MSM objects"; return ZKGPU_ERR_ARG; }
+    const std::shared_ptr<WsortBuffers> hd = leader->group == 1 ? leader->g1->sort_handle() : leader->g2->sort_handle();
+    return (follower->group == 1 ? follower->g1->share_sort_with(hd) : follower->g2->share_sort_with(hd)) ? 1 : 0; }); }
+int zkgpu_test_msm_set_stream(zkgpu_msm *h, int aux) { return guarded([&] { if (!h || aux < -1 || aux > 3) { g_err = "an MSM object and a stream in -1 .. 3"; return ZKGPU_ERR_ARG; }
+  if (h->group == 1) h->g1->set_stream(aux); else h->g2->set_stream(aux); return ZKGPU_OK; }); }
+static void msm_enqueue(zkgpu_msm *h, const Fe32 *z, const uint32_t *idx) { if (h->group == 1) h->g1->run(z, idx); else h->g2->run(z, idx); }
+static void msm_take(zkgpu_msm *h, uint8_t *out) { if (h->group == 1) g1_out(h->g1->result(), out); else g2_out(h->g2->result(), out); }
+int zkgpu_test_msm_run_pair(zkgpu_msm *leader, zkgpu_msm *follower, uint8_t *out_leader, uint8_t *out_follower) {
+  return guarded([&] { if (!leader || !follower || leader == follower || !leader->n || leader->n != follower->n || !out_leader || !out_follower) {
+      g_err = "two non-empty MSM objects of one size"; return ZKGPU_ERR_ARG; }
+    // both in flight before either result is taken, the follower over the leader's scalars, as in a proof
+    msm_enqueue(leader, leader->scalars.get(), nullptr); msm_enqueue(follower, leader->scalars.get(), nullptr);
+    msm_take(leader, out_leader); msm_take(follower, out_follower); return ZKGPU_OK; }); }
+// canonical elements -> Montgomery form on the device (synchronised)
+static void upload_fr(DevBuf<Fe32> &d, const uint8_t *z, size_t n) { d.upload((const Fe32 *)z, n); fr_to_mont_dev(d.get(), n); gpu_sync(); }
+int zkgpu_test_msm_run_indexed(zkgpu_msm *h, const uint8_t *z_all, size_t n_vars, const uint32_t *index, uint8_t *out) {
+  return guarded([&] { if (!h || !h->n || !z_all || !n_vars || !index || !out) { g_err = "a non-empty MSM object, scalars and an index"; return ZKGPU_ERR_ARG; }
+    for (size_t i = 0; i < h->n; i++) if (index[i] >= n_vars) { g_err = "an index beyond the scalars"; return ZKGPU_ERR_ARG; }
+    DevBuf<Fe32> dz(n_vars); DevBuf<uint32_t> di(h->n); upload_fr(dz, z_all, n_vars); di.upload(index, h->n);
+    msm_enqueue(h, dz.get(), di.get()); msm_take(h, out); return ZKGPU_OK; }); }
+int zkgpu_test_msm_run_tagged(zkgpu_msm *h, const uint8_t *z_all, size_t n_vars, const uint8_t *tags, const uint32_t *other_vars, size_t n_other, size_t n_other_bound,
+    const uint32_t *var_pos, const uint32_t *index, uint32_t base, uint8_t *out) {
+  return guarded([&] { if (!h || !h->n || !z_all || !n_vars || !tags || (n_other && !other_vars) || !out) { g_err = "a non-empty MSM object, an assignment and its tags"; return ZKGPU_ERR_ARG; }
+    // everything the kernels index with is checked here: they trust the prover's arrays
+    if (n_other_bound < n_other || n_other_bound >= (1u << 30) || n_vars >= (1ull << 31)) { g_err = "the list's bound"; return ZKGPU_ERR_ARG; }
+    for (size_t j = 0; j < n_other; j++) if (other_vars[j] >= n_vars) { g_err = "a listed variable beyond the assignment"; return ZKGPU_ERR_ARG; }
+    if (index) { for (size_t i = 0; i < h->n; i++) if (index[i] >= n_vars) { g_err = "an index beyond the assignment"; return ZKGPU_ERR_ARG; } }
+    else if ((size_t)base + h->n > n_vars) { g_err = "the slice leaves the assignment"; return ZKGPU_ERR_ARG; }
+    DevBuf<Fe32> dz(n_vars); DevBuf<uint8_t> dt(n_vars); DevBuf<uint32_t> dl(n_other_bound ? n_other_bound : 1), dn(1), dp(var_pos ? n_vars : 1), di(index ? h->n : 1);
+    upload_fr(dz, z_all, n_vars); dt.upload(tags, n_vars); dl.zero(); if (n_other) dl.upload(other_vars, n_other);
+    const uint32_t len = (uint32_t)n_other; dn.upload(&len, 1); if (var_pos) dp.upload(var_pos, n_vars); if (index) di.upload(index, h->n);
+    gpu_sync();
+    WitnessTags wt; wt.tags = dt.get(); wt.other_vars = dl.get(); wt.n_other = (uint32_t)n_other_bound; wt.n_other_dev = n_other_bound > n_other ? dn.get() : nullptr;
+    wt.var_pos = var_pos ? dp.get() : nullptr; wt.base = base;
+    if (h->group == 1) h->g1->run_tagged(dz.get(), wt, index ? di.get() : nullptr); else h->g2->run_tagged(dz.get(), wt, index ? di.get() : nullptr);
+    msm_take(h, out); return ZKGPU_OK; }); }
+static int msm_oneshot(int group,const uint8_t *points, const uint8_t *scalars, size_t n, int c, int fo, uint8_t *out) {
   zkgpu_msm *h = zkgpu_msm_create(group, points, n, c, fo);
   if (!h) return ZKGPU_ERR_RUNTIME;
   int rc = zkgpu_msm_set_scalars(h, scalars, n);

@@ -75,6 +75,13 @@ struct WitnessTags {
   const uint32_t *var_pos = nullptr;
   uint32_t base = 0;                    // plain query: point i belongs to variable base + i; indexed query: first position of this slice of the index list
 };
+// test entry points of the three-launch witness path (zkgpu_test_msm_wpath), both groups: out[0..19] = fused (0 / 1), c, W, NB | slots a bucket (WsortBuffers::cap), any
+// point at infinity, result slots, leader (1) or follower (0) of its sort | the sort is shared, the flag word of the last synchronised fused run (MsmCounters::pad[0],
+// read before a fallback: bit 0 a bucket overflowed, bit 1 a degenerate sum, G1 with its result slots from bit 8 on), that run's ones-list length, bucket lanes in use
+// (lane_off[NB]) | its slice length T, WFUSED_BUCKET_LANES, WFUSED_ONES_LANES, WFUSED_MIN_SLICE | bucket arrays, stream (0 main, 1..4 auxiliary), top = log2(NB), WTAIL_SLOTS.
+// test_w_state, after a synchronised fused run that did not fall back: what = 0 the current parity's fill (NB words), 1 lane_off (NB + 1), 2 the ones list, 3 every
+// bucket's entries end to end (min(fill, cap) words each).  Returns the words written; throws if cap_words is too small or the object is not on that path.
+constexpr int MSM_WPATH_WORDS = 20;
 class MsmG1 {
  public:
   // tables: precompute 2^(cw) P if the size cap allows; uniform: one-pass sort with overflow fallback (msm_impl.hpp)
@@ -110,6 +117,7 @@ class MsmG1 {
   // a bucket).  Returns the number of words written; throws if `cap_words` is too small or the object has no such state.
   static constexpr int TEST_PATH_WORDS = 24;
   void test_path(uint32_t out[TEST_PATH_WORDS]) const; size_t test_h_state(int what, uint32_t *out, size_t cap_words);
+  void test_wpath(uint32_t out[MSM_WPATH_WORDS]); size_t test_w_state(int what, uint32_t *out, size_t cap_words);
   struct Impl; std::unique_ptr<Impl> impl;
 };
 class MsmG2 {
@@ -121,6 +129,7 @@ class MsmG2 {
   void run_tagged(const Fe32 *z_all_dev, const WitnessTags &wt, const uint32_t *scalar_index_dev);
   std::shared_ptr<WsortBuffers> sort_handle() const; bool share_sort_with(const std::shared_ptr<WsortBuffers> &leader);
   host::HG2 result(); void set_label(const char *l); void set_stream(int aux); void split_ones_path();
+  void test_wpath(uint32_t out[MSM_WPATH_WORDS]); size_t test_w_state(int what, uint32_t *out, size_t cap_words);   // as MsmG1's
   struct Impl; std::unique_ptr<Impl> impl;
 };
 

@@ -49,4 +49,6 @@ size_t MsmG1::test_h_state(int what, uint32_t *out, size_t cap_words) {
   HIP_CHECK(hipMemcpy(out, src, words * 4, hipMemcpyDeviceToHost));
   return words;
 }
+void MsmG1::test_wpath(uint32_t out[MSM_WPATH_WORDS]) { impl->test_wpath(out); }
+size_t MsmG1::test_w_state(int what, uint32_t *out, size_t cap_words) { return impl->test_w_state(what, out, cap_words); }
 }  // namespace zk

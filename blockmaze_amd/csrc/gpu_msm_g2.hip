@@ -17,4 +17,6 @@ bool MsmG2::share_sort_with(const std::shared_ptr<WsortBuffers> &leader) {
 void MsmG2::run(const Fe32 *s, const uint32_t *idx) { impl->run(s, idx); }
 void MsmG2::run_tagged(const Fe32 *z_all, const WitnessTags &wt, const uint32_t *idx) { impl->run_tagged(z_all, wt, idx); }
 host::HG2 MsmG2::result() { impl->finish_sync(); return combine<host::HFq2, Fq2>(impl->host_sums(), impl->RS, impl->bitsum ? 1 : impl->c); }
+void MsmG2::test_wpath(uint32_t out[MSM_WPATH_WORDS]) { impl->test_wpath(out); }
+size_t MsmG2::test_w_state(int what, uint32_t *out, size_t cap_words) { return impl->test_w_state(what, out, cap_words); }
 }  // namespace zk

@@ -988,8 +988,9 @@ constexpr uint32_t WFUSED_BUCKET_LANES = 8192, WFUSED_ONES_LANES = 8192, WFUSED_
 // the same madd-2008-s in two steps, 2,275 instructions instead of ~4,400 — gathering from the tables with coordinates x 2^261 (Bases::points261 / groups261)
 // and leaving a Point29Rec per lane for k_wfold29 / k_wtail29 (htail29.cuh). COMPLETE in the lane (unlike the H accumulation): an operand equal to the
 // accumulator is doubled, one equal to its negative leaves the point at infinity — repeated query points are a property of real keys, not an accident. The fold
-// and the tail stay incomplete (two partial SUMS that coincide): ZZ = 0 (mod p) travels to a result slot, where k_wtail29 flags it and the MSM is repeated on
-// the general path.
+// and the tail are complete as well since round 6 (htail29.cuh: quad29_add<OPP> — two partial SUMS that coincide are added by way of the generator, opposite ones
+// give the point at infinity), the generator itself aside: should ZZ = 0 (mod p) still reach a result slot, k_wtail29 flags it and the MSM is repeated on the
+// general path. (The G2 path below is incomplete at all three places; tests/test_gpu_msm_w_path.py pins both down.)
 template <int UNIT>
 __global__ void __launch_bounds__(256) k_wacc_lanes29(const Affine<Fq> *__restrict__ points261, const Affine<Fq> *__restrict__ groups261,
     const uint32_t *__restrict__ entries, const uint32_t *__restrict__ fill, uint32_t cap, uint32_t NB,

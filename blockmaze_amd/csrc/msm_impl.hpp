@@ -48,6 +48,7 @@ struct MsmImpl {
   // prove_batch(64) 1,680 -> 1,860; 24 / 32 / 48: 1,843 / 1,858 / 1,835; profiles/r05_hacc_sweeps.txt).  One proof at a time keeps the short runs: its latency is the accumulation's last partial round.
   uint32_t h_run_crowded = 40; bool crowded = false;
   uint32_t last_ll = 0, last_flag = 0;   // lane exponent of the last combine, flag word of the last one-pass run (what a test reads back: MsmG1::test_path)
+  uint32_t last_wflag = 0, last_n_ones = 0;   // flag word and ones-list length of the last synchronised three-launch witness run, read before a fallback overwrites them (test_wpath)
   // witness MSMs in three launches (k_wsort / k_wacc / k_wtail); needs the fixed-base tables and at most 128 buckets
   bool wfused = false, ws_leader = true, overflow_noted = false; std::shared_ptr<WsortBuffers> ws;
   const Fe32 *last_scalars = nullptr; const uint32_t *last_index = nullptr;
@@ -128,7 +129,8 @@ struct MsmImpl {
   }
   static std::shared_ptr<const Bases> make_bases_impl(const RawAffine *host_points, size_t n_, int c_, bool fo, bool tables, bool uniform_hint) {
     auto b = std::make_shared<Bases>(); b->n = n_; b->c = c_; b->W = msm_num_windows(c_); b->WB = tables && use_precompute(n_, b->W) ? 1 : b->W;
-    if (c_ < 6 || c_ > 20 || b->W > MSM_MAX_WINDOWS) throw GpuError("msm: unsupported window size");
+    // (windows 4 and 5: 8 and 16 buckets — the three-launch witness path takes 16 buckets or more, and its constructor test below said so while this line refused them)
+    if (c_ < 4 || c_ > 20 || b->W > MSM_MAX_WINDOWS) throw GpuError("msm: unsupported window size");
     b->points = DevBuf<RawAffine>((n_ ? n_ : 1) * (size_t)(b->WB == 1 ? b->W : 1)); b->inf = DevBuf<uint8_t>(n_ ? n_ : 1);
     std::vector<uint8_t> flags(n_ ? n_ : 1, 0); const uint8_t zero[sizeof(RawAffine)] = {0};
     for (size_t i = 0; i < n_; i++) if (!memcmp(&host_points[i], zero, sizeof(RawAffine))) { flags[i] = 1; b->any_inf = true; }
@@ -308,6 +310,7 @@ struct MsmImpl {
   // after the stream has been synchronised: did a region of a one-pass sort overflow (or did the 29-bit accumulation meet an operand equal to +-its
   // accumulator)? Then repeat the last run on the general two-pass path (synchronously): any input stays correct, only the expected ones are fast.
   void finish_sync() { HIP_CHECK(hipStreamSynchronize(stream()));
+    if (wfused) { last_wflag = host_counters()->pad[0]; last_n_ones = host_counters()->n_ones; }
     if (wfused && host_counters()->pad[0]) {
       if (!overflow_noted) {
         overflow_noted = true;
@@ -340,6 +343,41 @@ struct MsmImpl {
         sc = prod_tmp.get();
       }
       const Fe32 *pb = prod_b; prod_b = nullptr; run_impl(sc, last_index); HIP_CHECK(hipStreamSynchronize(stream())); prod_b = pb; hsort = true; } }
+  // test entry points of the three-launch witness path (zkgpu_test_msm_wpath / _w_state; gpu.hpp: MSM_WPATH_WORDS): what the constructor decided, and what the last
+  // synchronised fused run left on the device.  The slice length is not stored anywhere: it is formed here from the fills as k_wacc_lanes29 forms it.
+  void test_wpath(uint32_t out[MSM_WPATH_WORDS]) {
+    HIP_CHECK(hipStreamSynchronize(stream()));
+    uint32_t lanes = 0, T = 0;
+    if (wfused) {
+      std::vector<uint32_t> fl(NB); HIP_CHECK(hipMemcpy(fl.data(), ws->fill.get() + (size_t)ws->parity * NB, NB * 4, hipMemcpyDeviceToHost));
+      HIP_CHECK(hipMemcpy(&lanes, lane_off.get() + NB, 4, hipMemcpyDeviceToHost));
+      uint32_t tot = 0; for (uint32_t b = 0; b < NB; b++) tot += std::min(fl[b], ws->cap);
+      T = std::max(WFUSED_MIN_SLICE, (tot + (WFUSED_BUCKET_LANES - NB) - 1) / (WFUSED_BUCKET_LANES - NB));
+    }
+    const uint32_t v[MSM_WPATH_WORDS] = {wfused ? 1u : 0u, (uint32_t)c, (uint32_t)W, NB, wfused ? ws->cap : 0u, any_inf ? 1u : 0u, (uint32_t)RS, ws_leader ? 1u : 0u,
+        wfused && ws->shared ? 1u : 0u, last_wflag, last_n_ones, lanes, T, WFUSED_BUCKET_LANES, WFUSED_ONES_LANES, WFUSED_MIN_SLICE, (uint32_t)WB, (uint32_t)(stream_id + 1),
+        31 - (uint32_t)__builtin_clz(NB), (uint32_t)WTAIL_SLOTS};
+    memcpy(out, v, sizeof v);
+  }
+  size_t test_w_state(int what, uint32_t *out, size_t cap_words) {
+    if (!wfused) throw GpuError("msm: no three-launch witness state on this object");
+    HIP_CHECK(hipStreamSynchronize(stream()));
+    const uint32_t *fill_dev = ws->fill.get() + (size_t)ws->parity * NB;
+    auto fetch = [&](const uint32_t *src, size_t words) { if (words > cap_words) throw GpuError("msm: state buffer too small");
+      if (words) HIP_CHECK(hipMemcpy(out, src, words * 4, hipMemcpyDeviceToHost)); return words; };
+    switch (what) {
+      case 0: return fetch(fill_dev, NB);
+      case 1: return fetch(lane_off.get(), (size_t)NB + 1);
+      case 2: return fetch(ws->ones.get(), std::min<size_t>(last_n_ones, n));
+      case 3: { std::vector<uint32_t> fl(NB); HIP_CHECK(hipMemcpy(fl.data(), fill_dev, NB * 4, hipMemcpyDeviceToHost));
+        size_t words = 0; for (uint32_t b = 0; b < NB; b++) words += std::min(fl[b], ws->cap);
+        if (words > cap_words) throw GpuError("msm: state buffer too small");
+        size_t at = 0; for (uint32_t b = 0; b < NB; b++) { const size_t m = std::min(fl[b], ws->cap);
+          if (m) HIP_CHECK(hipMemcpy(out + at, ws->entries.get() + (size_t)b * ws->cap, m * 4, hipMemcpyDeviceToHost)); at += m; }
+        return words; }
+      default: throw GpuError("msm: unknown state");
+    }
+  }
   // sum_i (a_i b_i z) P_i; only on the H path, where the product is formed inside the sort kernel
   void run_product(const Fe32 *a, const Fe32 *b, const Fe32 *z, bool z_is_table) {
     if (!hsort) throw GpuError("msm: run_product needs the one-pass sort");

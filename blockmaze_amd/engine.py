@@ -240,11 +240,50 @@ class ResidentMsm:
         p = self.path(); cap = {"counts": p.NB, "offsets": p.NB, "group_n": p.groups, "entries": p.groups * p.region, "hb29": p.NB * 48}[what]
         out = np.zeros(max(cap, 1), dtype=np.uint32); words = ctypes.c_size_t(0)
         _check(lib().zkgpu_test_msm_h_state(ctypes.c_void_p(self.h), self.H_STATE[what], _u32(out), ctypes.c_size_t(out.size), ctypes.byref(words))); return out[:words.value]
+    # test entry points of the witness MSMs' three-launch path, both groups (include/zkgpu.h: zkgpu_test_msm_wpath and what follows it)
+    WPATH_FIELDS = ("fused", "c", "W", "NB", "cap", "any_inf", "RS", "leader", "shared", "flag", "n_ones", "lanes", "T", "bucket_lanes", "ones_lanes", "min_slice", "WB",
+                    "stream", "top", "tail_slots")
+    W_STATE = {"fill": 0, "lane_off": 1, "ones": 2, "entries": 3}
+    def wpath(self):
+        """what the object decided when it was created and what its last synchronised fused run reported, as a namespace of ints; fused, leader and shared are bools"""
+        import types
+        out = np.zeros(len(self.WPATH_FIELDS), dtype=np.uint32); _check(lib().zkgpu_test_msm_wpath(ctypes.c_void_p(self.h), _u32(out)))
+        d = {k: int(v) for k, v in zip(self.WPATH_FIELDS, out)}
+        for k in ("fused", "leader", "shared"): d[k] = bool(d[k])
+        return types.SimpleNamespace(**d)
+    def w_state(self, what):
+        """device state of the last fused run (only meaningful when it did not fall back): uint32 words, see W_STATE; entries: every bucket's end to end"""
+        p = self.wpath(); cap = {"fill": p.NB, "lane_off": p.NB + 1, "ones": self.n, "entries": p.NB * p.cap}[what]
+        out = np.zeros(max(cap, 1), dtype=np.uint32); words = ctypes.c_size_t(0)
+        _check(lib().zkgpu_test_msm_w_state(ctypes.c_void_p(self.h), self.W_STATE[what], _u32(out), ctypes.c_size_t(out.size), ctypes.byref(words))); return out[:words.value]
+    def share_sort(self, leader):
+        """this object takes the leader's sort of the scalars; False if share_sort_with refused"""
+        rc = int(lib().zkgpu_test_msm_share_sort(ctypes.c_void_p(self.h), ctypes.c_void_p(leader.h)))
+        if rc < 0: _check(rc)
+        return bool(rc)
+    def set_stream(self, aux): _check(lib().zkgpu_test_msm_set_stream(ctypes.c_void_p(self.h), int(aux)))
+    def _out(self): return np.zeros(8 if self.group == 1 else 16, dtype=np.uint64)
+    def run_indexed(self, z_all, index):
+        """point i takes the scalar z_all[index[i]]"""
+        z = np.ascontiguousarray(z_all, dtype=np.uint64).reshape(-1, 4); idx = np.ascontiguousarray(index, dtype=np.uint32); assert idx.shape == (self.n,); out = self._out()
+        _check(lib().zkgpu_test_msm_run_indexed(ctypes.c_void_p(self.h), _bytes(z), ctypes.c_size_t(z.shape[0]), _u32(idx), _bytes(out))); return out
+    def run_tagged(self, z_all, tags, other_vars, n_other_bound=None, var_pos=None, index=None, base=0):
+        """the sort from the assignment's tags (k_wsort_tagged): z_all with variable 0 = ONE, a tag byte a variable, the list of the variables tagged 2"""
+        z = np.ascontiguousarray(z_all, dtype=np.uint64).reshape(-1, 4); nv = z.shape[0]; tags = np.ascontiguousarray(tags, dtype=np.uint8); assert tags.shape == (nv,)
+        ov = np.ascontiguousarray(other_vars, dtype=np.uint32).reshape(-1); bound = ov.size if n_other_bound is None else int(n_other_bound)
+        vp = np.ascontiguousarray(var_pos, dtype=np.uint32) if var_pos is not None else None; idx = np.ascontiguousarray(index, dtype=np.uint32) if index is not None else None
+        assert (vp is None or vp.shape == (nv,)) and (idx is None or idx.shape == (self.n,)); out = self._out()
+        _check(lib().zkgpu_test_msm_run_tagged(ctypes.c_void_p(self.h), _bytes(z), ctypes.c_size_t(nv), _bytes(tags), _u32(ov) if ov.size else None, ctypes.c_size_t(ov.size),
+                                               ctypes.c_size_t(bound), _u32(vp), _u32(idx), ctypes.c_uint32(base), _bytes(out))); return out
     def close(self):
         if self.h: lib().zkgpu_msm_destroy(ctypes.c_void_p(self.h)); self.h = None
     def __del__(self):
         try: self.close()
         except Exception: pass
+
+def run_pair(leader, follower):
+    """the leader's run and the follower's, over the leader's scalars, both in flight before either result is taken -> (leader's sum, follower's sum)"""
+    a, b = leader._out(), follower._out(); _check(lib().zkgpu_test_msm_run_pair(ctypes.c_void_p(leader.h), ctypes.c_void_p(follower.h), _bytes(a), _bytes(b))); return a, b
 
 def domain_size(min_size): return int(lib().zkgpu_domain_size(min_size))
 def domain_transform(min_size, op, data):

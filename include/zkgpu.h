@@ -91,6 +91,34 @@ int zkgpu_test_msm_path(zkgpu_msm *h, uint32_t out[24]);
 int zkgpu_test_msm_set_crowded(zkgpu_msm *h, int on);
 int zkgpu_test_msm_run_product(zkgpu_msm *h, const uint8_t *a, const uint8_t *b, const uint8_t *z, int z_is_table, uint8_t out[64]);
 int zkgpu_test_msm_h_state(zkgpu_msm *h, int what, uint32_t *out, size_t cap_words, size_t *words);
+/* Test entry points of the witness MSMs' three-launch path (filter_ones bit 0, fixed-base tables, 16 to 128 buckets: windows 5 to 8), G1 and G2 objects alike; they add
+   no product behaviour.
+   zkgpu_test_msm_wpath: 20 words: on that path (0 / 1), window bits c, windows W, buckets NB | entry slots a bucket (cap), any key point at infinity, result slots,
+   leader (1) or follower (0) of its sort | the sort is shared (0 / 1), the flag word the last synchronised fused run raised — read before the repeat on the general path
+   (0: none; bit 0: a bucket of the sort overflowed; bit 1: a degenerate sum in the fold or the tail, on G1 with its result slots from bit 8 on, bit 31 = the sum of the
+   ones) —, the length of that run's list of ones, the bucket lanes it used (lane_off[NB]) | its slice length T (entries a lane), and the constants the model restates:
+   bucket lanes, ones lanes, the smallest slice | bucket arrays, stream (0 main, 1 .. 4 auxiliary), log2(NB), result slots of the tail.
+   zkgpu_test_msm_w_state: what the last synchronised fused run left on the device — only meaningful after a run that did not fall back: what = 0 entries per bucket
+   (NB words), 1 the first lane of every bucket (NB + 1 words), 2 the list of ones (an entry = 15 g + v - 1: the subset v of the four points 4g .. 4g + 3), 3 every
+   bucket's entries end to end, min(fill, cap) words each (an entry = table index i + w n | sign in bit 31).  *words = how many words were written.
+   zkgpu_test_msm_share_sort: the follower takes the leader's sort (MSMs over one scalar vector: A and L, B1 and the G2 half of B); returns 1 accepted, 0 refused (either
+   side off the path, another size or window), below 0 an error.  The leader is a G1 or a G2 object.
+   zkgpu_test_msm_set_stream: -1 the main stream, 0 .. 3 an auxiliary one.
+   zkgpu_test_msm_run_pair: the leader's run, then the follower's over the LEADER's scalars (zkgpu_msm_set_scalars on the leader), both enqueued before either result is
+   taken.
+   zkgpu_test_msm_run_indexed: point i takes the scalar z_all[index[i]] (n_vars canonical elements; index: one word a point of the object).
+   zkgpu_test_msm_run_tagged: the sort from an assignment's tags.  z_all: n_vars canonical elements, variable 0 = ONE; tags: a byte a variable (0 zero, 1 one, 2 listed);
+   other_vars: the n_other variables tagged 2, ascending; n_other_bound > n_other: the launch is sized by the bound and the length travels in device memory; var_pos
+   (or null): n_vars words, a variable's position in the whole index list, 0xffffffff = none; index (or null): one word a point; base: plain query — point i belongs
+   to variable base + i; indexed — the first position of this slice.  Every index is checked against n_vars before anything is launched. */
+int zkgpu_test_msm_wpath(zkgpu_msm *h, uint32_t out[20]);
+int zkgpu_test_msm_w_state(zkgpu_msm *h, int what, uint32_t *out, size_t cap_words, size_t *words);
+int zkgpu_test_msm_share_sort(zkgpu_msm *follower, zkgpu_msm *leader);
+int zkgpu_test_msm_set_stream(zkgpu_msm *h, int aux);
+int zkgpu_test_msm_run_pair(zkgpu_msm *leader, zkgpu_msm *follower, uint8_t *out_leader, uint8_t *out_follower);
+int zkgpu_test_msm_run_indexed(zkgpu_msm *h, const uint8_t *z_all, size_t n_vars, const uint32_t *index, uint8_t *out);
+int zkgpu_test_msm_run_tagged(zkgpu_msm *h, const uint8_t *z_all, size_t n_vars, const uint8_t *tags, const uint32_t *other_vars, size_t n_other, size_t n_other_bound,
+    const uint32_t *var_pos, const uint32_t *index, uint32_t base, uint8_t *out);
 
 /* ---- evaluation domains --------------------------------------------------------------------------------------------- */
 size_t zkgpu_domain_size(size_t min_size);          /* m chosen by get_evaluation_domain for this minimum size, 0 if none */

@@ -86,10 +86,14 @@ def test_witness_msm_fast_path_edge_cases(group):
     n = 3000 if group == 1 else 600; g = o.SplitMix64(500 + group); P = (o.g1_consecutive if group == 1 else o.g2_consecutive)(g.field(), n)
     ref = (lambda K: o.msm_g1(P, K, mixed=True)) if group == 1 else (lambda K: o.msm_g2(P, K, mixed=True)); dec = o.g1_from if group == 1 else o.g2_from
     m = e.ResidentMsm(group, P, 8, filter_ones=True)
-    def check(K): m.set_scalars(K); assert dec(m.run())[0] == ref(K)
+    # (G1 is complete on this path — lanes, fold and tail —, so only a bucket with more entries than its 8,192 slots repeats a G1 run on the general path; a G2 run
+    #  is also repeated when two partial sums of these points in arithmetic progression coincide: tests/test_gpu_msm_w_path.py predicts that from the device's state)
+    def check(K, repeats=0):
+        before = e.general_path_repeats(); m.set_scalars(K); assert dec(m.run())[0] == ref(K); moved = e.general_path_repeats() - before
+        assert group == 2 or moved == repeats, "repeats of the general path: %d, expected %d" % (moved, repeats)
     check(witness_like_scalars(77, n))
     check(o.to_arr([1] * n)); check(o.to_arr([0] * n)); check(o.to_arr([2 + (i % 251) for i in range(n)]))
-    check(o.to_arr([0x0101010101010101] * n))                                                      # eight digits equal to 1: one bucket holds 8 n entries
+    check(o.to_arr([0x0101010101010101] * n), repeats=1)                                           # eight digits equal to 1: one bucket holds 8 n entries (24,000 at n = 3,000: over the slots)
     one = [0] * n; one[n // 2] = o.R_MOD - 1; check(o.to_arr(one))
     check(o.to_arr([o.R_MOD - 1 - i for i in range(n)]))                                           # full-width values only: 32 digits each
     check(witness_like_scalars(78, n)); m.close()
@@ -143,8 +147,12 @@ def test_witness_path_degenerate_points_fall_back_and_stay_exact(group):
     def neg(pt):
         r = pt.copy(); ys = o.from_arr(pt[half:].reshape(-1, 4)); r[half:] = o.to_arr([(o.Q_MOD - y) % o.Q_MOD for y in ys]).reshape(-1); return r
     def run(P, K):
+        # (G1: no bucket comes near its 8,192 slots here, and lanes, fold and tail are complete since quad29_add<OPP> — none of these runs is repeated; G2: the
+        #  incomplete additions flag, tests/test_gpu_msm_w_path.py says when)
+        before = e.general_path_repeats()
         m = e.ResidentMsm(group, P, 8, filter_ones=True); m.set_scalars(K); assert dec(m.run())[0] == ref(P, K)
         K2 = witness_like_scalars(31, len(P)); m.set_scalars(K2); assert dec(m.run())[0] == ref(P, K2); m.close()
+        assert group == 2 or e.general_path_repeats() == before
     ones = o.to_arr([1] * n); small = o.to_arr([5] * n); wl = witness_like_scalars(30 + group, n)
     same = np.repeat(base[:1], n, axis=0); run(same, ones); run(same, small); run(same, wl)                  # every point equal
     P = base.copy()
